@@ -15,12 +15,25 @@ Heaps-law fit to methods.txt's unique-name curve (tools/derive_label_vocab.py)
 and stated in config.
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config top11]
+                       [--dump-outputs DIR] [--full]
 For N>1 the driver launches via torch.distributed.run.
+
+A plain run sets up, warms up, times the K steps and prints one JSON result
+line.  --dump-outputs DIR additionally writes what the last timed step
+returned (and the parameters it updated) as DIR/<name>.npy, float32, so two
+builds can be compared output for output.  Model init, batches and the
+dropout RNG are seeded, and that last step is run from the seeded initial
+model and optimizer state (put back with the clock stopped), so what it
+computes is a function of the arguments alone and repeats from run to run.
+--full is where any measurement beyond the headline figure belongs; the
+benchmark has none today (other modes and configs are runs of their own,
+selected with --mode / --config / --real-pipeline), so it changes nothing.
 """
 
 from __future__ import annotations
 
 import argparse
+import copy
 import json
 import os
 import sys
@@ -85,7 +98,16 @@ def main() -> None:
     ap.add_argument("--methods", type=int, default=605945,
                     help="--real-pipeline corpus size (default: top11's "
                          "method count)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's "
+                         "results as DIR/<name>.npy (float32; large arrays "
+                         "as a fixed seeded sample of rows/columns)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement; a plain run "
+                         "does only what the headline figure needs (there "
+                         "are no secondary measurements at present)")
     args = ap.parse_args()
+    assert args.steps >= 1, "--steps must be at least 1"
 
     cfg = CONFIGS[args.config]
     ctx = init_distributed("cuda" if torch.cuda.is_available() else "cpu")
@@ -95,6 +117,9 @@ def main() -> None:
     )
     device = ctx.device
     on_gpu = device.type == "cuda"
+    # dropout draws from the global seed (torch's default one differs from
+    # process to process); fix it so every run sees the same masks
+    torch.manual_seed(123 + ctx.rank)
 
     opt = Option(
         terminal_count=cfg["terminal_count"], path_count=cfg["path_count"],
@@ -162,14 +187,16 @@ def main() -> None:
 
         batch_iter = cycle()
 
-    def step(i: int) -> None:
+    last = {}  # what the last timed step returned (--dump-outputs)
+
+    def step(i: int, keep: bool = False) -> None:
         if batch_iter is not None:
             hb = next(batch_iter)
             s, p, e, y = (hb["starts"], hb["paths"], hb["ends"], hb["label"])
         else:
             s, p, e, y = pool[i % len(pool)]
         ddp.zero_grad()
-        outputs, _, _ = model(s, p, e, y)
+        outputs, cv, attn = model(s, p, e, y)
         loss = model.loss(outputs, y, class_weight)
         loss.backward()
         if on_gpu:
@@ -177,6 +204,9 @@ def main() -> None:
         else:
             ddp.finish()
             optim.step()
+        if keep:
+            last.update(loss=loss, outputs=outputs, code_vector=cv,
+                        attention=attn)
 
     # hipGraph-captured whole training step (N=1 pool mode) — opt-in
     # EXPERIMENT (C2V_GRAPH_STEP=1): capture works and replays bitwise-
@@ -197,10 +227,13 @@ def main() -> None:
             def graph_body():
                 s, p, e, y = static
                 ddp.zero_grad()
-                outputs, _, _ = model(s, p, e, y)
+                outputs, cv, attn = model(s, p, e, y)
                 loss = model.loss(outputs, y, class_weight)
                 loss.backward()
                 ddp.finish_and_step(optim)
+                # static graph memory: holds the latest replay's results
+                last.update(loss=loss, outputs=outputs, code_vector=cv,
+                            attention=attn)
 
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
@@ -218,7 +251,7 @@ def main() -> None:
             with torch.cuda.graph(graph):
                 graph_body()
 
-            def graphed_step(i: int) -> None:
+            def graphed_step(i: int, keep: bool = False) -> None:
                 for dst, src in zip(static, pool[i % len(pool)]):
                     dst.copy_(src, non_blocking=True)
                 graph.replay()
@@ -230,6 +263,13 @@ def main() -> None:
                 print(f"# hipGraph capture unavailable, eager step: {exc}",
                       file=sys.stderr)
 
+    # --dump-outputs: keep the seeded starting point.  Over many steps the
+    # trajectory is not bit-reproducible (the table-grad scatter sums each
+    # row's contributions in atomic-placement order, and one flipped bf16
+    # rounding then grows with training), so the step whose results are
+    # dumped is run from this state: its inputs are the same in every run.
+    initial = snapshot_state(model, optim) if args.dump_outputs else None
+
     for i in range(args.warmup):
         step(i)
 
@@ -238,13 +278,25 @@ def main() -> None:
     if on_gpu:
         torch.cuda.synchronize()
     t0 = time.perf_counter()
+    keep_at = args.steps - 1 if args.dump_outputs else -1
+    paused = 0.0
     for i in range(args.steps):
-        step(i)
+        if i == keep_at:
+            # the dumped step starts from the seeded initial state; putting
+            # it back is not part of a step, so the clock stops meanwhile
+            if on_gpu:
+                torch.cuda.synchronize()
+            t_pause = time.perf_counter()
+            restore_state(initial)
+            if on_gpu:
+                torch.cuda.synchronize()
+            paused = time.perf_counter() - t_pause
+        step(i, i == keep_at)
     if on_gpu:
         torch.cuda.synchronize()
     if ctx.initialized:
         torch.distributed.barrier()
-    elapsed = time.perf_counter() - t0
+    elapsed = time.perf_counter() - t0 - paused
 
     # MAX over ranks
     if ctx.initialized:
@@ -255,6 +307,12 @@ def main() -> None:
     contexts_per_step = world * B * C
     value = contexts_per_step * args.steps / elapsed
     ms_per_step = elapsed / args.steps * 1000.0
+
+    if args.dump_outputs and ctx.is_rank0:
+        arrays = {k: v.detach() for k, v in last.items()}
+        arrays.update(
+            ("param_" + n, p.detach()) for n, p in model.named_parameters())
+        dump_outputs(args.dump_outputs, arrays)
 
     if ctx.is_rank0:
         print(json.dumps({
@@ -294,6 +352,66 @@ def main() -> None:
         }))
 
 
+def snapshot_state(model, optim):
+    """Copies of everything a training step reads and updates: parameters,
+    optimizer state and the host RNG (the dropout counter restarts at 0)."""
+    live = [p.data for p in model.parameters()]
+    if isinstance(optim, FusedAdam):
+        for st in optim.state.values():
+            live += [t for t in st.values() if t is not None]
+        live.append(optim.bc_pow)
+        host = optim.step_count
+    else:
+        host = copy.deepcopy(optim.state_dict())
+    return (optim, live, [t.clone() for t in live], host,
+            torch.get_rng_state())
+
+
+def restore_state(snap) -> None:
+    from code2vec_amd.ops import functional as Fn
+
+    optim, live, saved, host, rng_state = snap
+    with torch.no_grad():
+        for t, c in zip(live, saved):
+            t.copy_(c)
+    if isinstance(optim, FusedAdam):
+        optim.step_count = host
+    else:
+        optim.load_state_dict(copy.deepcopy(host))
+    torch.set_rng_state(rng_state)
+    Fn.reseed_dropout_rng(torch.initial_seed())
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+DUMP_MAX_ROWS = 16384  # rows kept of a 2-D array (the big tables)
+DUMP_MAX_COLS = 2048  # columns kept of a 2-D array (the logits)
+
+
+def dump_outputs(out_dir: str, arrays) -> None:
+    """Write each tensor as out_dir/<name>.npy in float32.
+
+    Arrays too large to keep whole are cut to a fixed sample: DUMP_MAX_ROWS
+    sorted row indices (DUMP_MAX_COLS column indices for the wide logits),
+    drawn by a generator seeded with the axis length, so the same indices
+    are chosen by every run and every build.
+    """
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        if t.dim() == 2:
+            for dim, cap in ((0, DUMP_MAX_ROWS), (1, DUMP_MAX_COLS)):
+                n = t.shape[dim]
+                if n > cap:
+                    idx = np.sort(np.random.default_rng(n).choice(
+                        n, size=cap, replace=False))
+                    t = t.index_select(
+                        dim, torch.from_numpy(idx).to(t.device))
+        a = t.float().cpu().numpy()
+        total += a.nbytes
+        assert total <= DUMP_LIMIT_BYTES, (name, total)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def run_infer(args, cfg, ctx, model, pool) -> None:
     """Inference-only: hipGraph-captured forward, code-vector batches/s."""
     from code2vec_amd.engine.infer import GraphedInference
@@ -318,11 +436,14 @@ def run_infer(args, cfg, ctx, model, pool) -> None:
         torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(i)
+        out = step(i)
     if device.type == "cuda":
         torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     value = ctx.world_size * B * C * args.steps / elapsed
+    if args.dump_outputs and ctx.is_rank0:
+        dump_outputs(args.dump_outputs, dict(
+            zip(("outputs", "code_vector", "attention"), out)))
     if ctx.is_rank0:
         print(json.dumps({
             "metric": "infer_path_contexts_per_sec",

@@ -138,8 +138,10 @@ def _worker_trainer(rank, world, port, tmpdir, result_file, n_methods=40):
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
 
+    # one copy per rank (same seed => identical content): a shared directory
+    # lets one rank truncate a file the other is already parsing
     files = write_synthetic_corpus(
-        os.path.join(tmpdir, "data"),
+        os.path.join(tmpdir, f"data{rank}"),
         SyntheticSpec(n_methods=n_methods, n_terminals=60, n_paths=50,
                       max_contexts=16, seed=5),
     )

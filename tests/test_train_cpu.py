@@ -83,7 +83,7 @@ def test_cli_variable_task(tmp_path, tiny_corpus, shuffle):
     assert (out_dir / "code.vec").exists()
 
 
-def test_training_reduces_loss(tiny_corpus):
+def test_training_reduces_loss(tmp_path, tiny_corpus):
     """Loss-curve sanity: a few epochs on the tiny corpus reduce train loss."""
     reader = CorpusReader(
         tiny_corpus["corpus_path"], tiny_corpus["path_idx_path"],
@@ -104,8 +104,9 @@ def test_training_reduces_loss(tiny_corpus):
 
     class A:  # minimal args carrier
         max_epoch = 1; lr = 0.01; beta_min = 0.9; beta_max = 0.999
-        weight_decay = 0.0; model_path = "/tmp/c2v_test_out"
-        vectors_path = "/tmp/c2v_test_out/code.vec"; test_result_path = None
+        weight_decay = 0.0; model_path = str(tmp_path / "out")
+        vectors_path = str(tmp_path / "out" / "code.vec")
+        test_result_path = None
         env = None; print_sample_cycle = 0; eval_method = "subtoken"
         random_seed = 1; batch_size = 16
 
@@ -204,7 +205,7 @@ def test_print_sample_runs(tmp_path, tiny_corpus, caplog):
         assert any("label" in r.getMessage() for r in caplog.records)
 
 
-def test_seed_determinism_end_to_end(tiny_corpus):
+def test_seed_determinism_end_to_end(tmp_path, tiny_corpus):
     """Same seed => identical epoch-0 loss (the reference's unseeded
     run-to-run variance is a design delta we intentionally remove)."""
     def one_loss():
@@ -228,8 +229,9 @@ def test_seed_determinism_end_to_end(tiny_corpus):
 
         class A:
             max_epoch = 1; lr = 0.01; beta_min = 0.9; beta_max = 0.999
-            weight_decay = 0.0; model_path = "/tmp/c2v_det"
-            vectors_path = "/tmp/c2v_det/code.vec"; test_result_path = None
+            weight_decay = 0.0; model_path = str(tmp_path / "out")
+            vectors_path = str(tmp_path / "out" / "code.vec")
+            test_result_path = None
             env = None; print_sample_cycle = 0; eval_method = "subtoken"
             random_seed = 21; batch_size = 16
 
@@ -326,6 +328,15 @@ def test_floyd_metric_line_format(tmp_path, tiny_corpus, capsys):
     assert "epoch 0" in out
 
 
+def _cpu_only_env():
+    """Environment for the CPU-fallback bench rehearsals: hide every GPU so
+    they take the torch/gloo path on a machine that has one, too."""
+    env = dict(os.environ)
+    env["HIP_VISIBLE_DEVICES"] = "-1"
+    env["CUDA_VISIBLE_DEVICES"] = "-1"
+    return env
+
+
 def test_bench_driver_contract(tmp_path):
     """bench.py is the driver's measurement contract: with no GPU it must
     still run (torch reference model), finish quickly at the tiny config,
@@ -335,10 +346,13 @@ def test_bench_driver_contract(tmp_path):
     import subprocess
 
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dump = tmp_path / "dump"
     out = subprocess.run(
         [sys.executable, os.path.join(repo, "bench.py"), "--config", "tiny",
-         "--steps", "2", "--warmup", "1", "--pool", "2"],
-        capture_output=True, text=True, timeout=420, cwd=repo)
+         "--steps", "2", "--warmup", "1", "--pool", "2",
+         "--dump-outputs", str(dump)],
+        capture_output=True, text=True, timeout=420, cwd=repo,
+        env=_cpu_only_env())
     assert out.returncode == 0, out.stderr[-2000:]
     line = out.stdout.strip().splitlines()[-1]
     d = json.loads(line)
@@ -352,11 +366,45 @@ def test_bench_driver_contract(tmp_path):
     assert isinstance(d["config"], dict) and "global_batch" in d["config"]
     assert d["dtype"] == "fp32"  # CPU fallback states its real dtype
 
-    # --mode infer carries the same contract shape
+    # --dump-outputs: the last timed step's results and updated parameters,
+    # float32 .npy, finite, within the 64 MB budget
+    import numpy as np
+
+    names = {f.name for f in dump.iterdir()}
+    assert {"loss.npy", "outputs.npy", "code_vector.npy", "attention.npy",
+            "param_terminal_embedding.npy",
+            "param_output_weight.npy"} <= names, names
+    total = 0
+    for f in dump.iterdir():
+        a = np.load(f)
+        assert a.dtype == np.float32 and np.isfinite(a).all(), f.name
+        total += a.nbytes
+    assert total <= 64 * 1000 * 1000
+    assert np.load(dump / "code_vector.npy").shape == (32, 100)
+    assert np.load(dump / "attention.npy").shape == (32, 200)
+
+    # the dumped step runs from the seeded initial state on the batch its
+    # index selects, so another run whose last step takes the same batch
+    # (4 steps, no warmup: batch 3 % 2 == 1 again) writes identical files
+    dump2 = tmp_path / "dump2"
     out = subprocess.run(
         [sys.executable, os.path.join(repo, "bench.py"), "--config", "tiny",
-         "--mode", "infer", "--steps", "2", "--warmup", "1", "--pool", "2"],
-        capture_output=True, text=True, timeout=420, cwd=repo)
+         "--steps", "4", "--warmup", "0", "--pool", "2",
+         "--dump-outputs", str(dump2)],
+        capture_output=True, text=True, timeout=420, cwd=repo,
+        env=_cpu_only_env())
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert {f.name for f in dump2.iterdir()} == names
+    for name in names:
+        assert np.array_equal(np.load(dump / name), np.load(dump2 / name)), name
+
+    # --mode infer carries the same contract shape; --full is accepted
+    out = subprocess.run(
+        [sys.executable, os.path.join(repo, "bench.py"), "--config", "tiny",
+         "--mode", "infer", "--steps", "2", "--warmup", "1", "--pool", "2",
+         "--full"],
+        capture_output=True, text=True, timeout=420, cwd=repo,
+        env=_cpu_only_env())
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads(out.stdout.strip().splitlines()[-1])
     assert d["metric"] == "infer_path_contexts_per_sec"
@@ -381,7 +429,8 @@ def test_bench_torchrun_world2_cpu():
          "--master-port", str(port),
          os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "2",
          "--warmup", "1", "--config", "tiny", "--pool", "2"],
-        capture_output=True, text=True, timeout=540, cwd=repo)
+        capture_output=True, text=True, timeout=540, cwd=repo,
+        env=_cpu_only_env())
     assert out.returncode == 0, out.stderr[-2000:]
     json_lines = [ln for ln in out.stdout.splitlines()
                   if ln.startswith("{") and "path_contexts_per_sec" in ln]
@@ -409,7 +458,8 @@ def test_bench_torchrun_world4_cpu():
          "--master-port", str(port),
          os.path.join(repo, "bench.py"), "--gpus", "4", "--steps", "2",
          "--warmup", "1", "--config", "tiny", "--pool", "2"],
-        capture_output=True, text=True, timeout=540, cwd=repo)
+        capture_output=True, text=True, timeout=540, cwd=repo,
+        env=_cpu_only_env())
     assert out.returncode == 0, out.stderr[-2000:]
     json_lines = [ln for ln in out.stdout.splitlines()
                   if ln.startswith("{") and "path_contexts_per_sec" in ln]
