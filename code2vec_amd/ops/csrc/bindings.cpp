@@ -72,6 +72,9 @@ void launch_slab_sum_f32(const float*, float*, int, int, hipStream_t);
 void launch_colsum_bf16(const void*, float*, long, long, hipStream_t);
 void launch_row_max_argmax(const void*, float*, long*, long, long,
                            hipStream_t);
+int row_topk_chunk();
+void launch_row_topk(const void*, int, long, long, int, void*, float*, float*,
+                     float*, long*, float*, hipStream_t);
 void launch_head_bwd_prep(const long*, const float*, const float*,
                           const float*, const float*, float*, long,
                           hipStream_t);
@@ -697,6 +700,50 @@ void row_max_argmax(torch::Tensor x, torch::Tensor vals, torch::Tensor idx) {
                         idx.data_ptr<long>(), B, L, cur_stream());
 }
 
+// K19: per-row top-k + log-sum-exp.  x: [B, L] bf16 or f32; vals f32
+// [B, k], idx i64 [B, k] (descending value, ties to the smallest column),
+// lse f32 [B].  part (i64 [B, nchunk, 16]) and pm/ps (f32 [B, nchunk])
+// are the per-chunk partials, only read when L > chunk; `chunk` is the
+// caller's idea of the chunk width and must match the compiled one.
+void row_topk(torch::Tensor x, int64_t k, int64_t chunk, torch::Tensor part,
+              torch::Tensor pm, torch::Tensor ps, torch::Tensor vals,
+              torch::Tensor idx, torch::Tensor lse) {
+  CHK_CUDA(x); CHK_CONTIG(x);
+  TORCH_CHECK(x.dim() == 2, "row_topk: x must be [B, L]");
+  const bool is_f32 = x.scalar_type() == torch::kFloat32;
+  TORCH_CHECK(is_f32 || x.scalar_type() == torch::kBFloat16,
+              "row_topk: x must be bf16 or f32");
+  const long B = x.size(0), L = x.size(1);
+  TORCH_CHECK(chunk == row_topk_chunk(), "row_topk: chunk width ", chunk,
+              " != compiled ", row_topk_chunk());
+  TORCH_CHECK(k >= 1 && k <= 16, "row_topk: k must be in 1..16, got ", k);
+  TORCH_CHECK(k <= L, "row_topk: k = ", k, " exceeds row length ", L);
+  TORCH_CHECK(L < (1L << 31), "row_topk: L must be < 2^31");
+  const long nchunk = (L + chunk - 1) / chunk;
+  TORCH_CHECK(B * nchunk < (1L << 31), "row_topk: grid too large");
+  CHK_CUDA(vals); CHK_CONTIG(vals); CHK_DT(vals, torch::kFloat32);
+  CHK_CUDA(idx); CHK_CONTIG(idx); CHK_DT(idx, torch::kInt64);
+  CHK_CUDA(lse); CHK_CONTIG(lse); CHK_DT(lse, torch::kFloat32);
+  TORCH_CHECK(vals.numel() == B * k && idx.numel() == B * k &&
+              lse.numel() == B, "row_topk: output shapes");
+  void* pp = nullptr;
+  float* pmp = nullptr;
+  float* psp = nullptr;
+  if (nchunk > 1) {
+    CHK_CUDA(part); CHK_CONTIG(part); CHK_DT(part, torch::kInt64);
+    CHK_CUDA(pm); CHK_CONTIG(pm); CHK_DT(pm, torch::kFloat32);
+    CHK_CUDA(ps); CHK_CONTIG(ps); CHK_DT(ps, torch::kFloat32);
+    TORCH_CHECK(part.numel() >= B * nchunk * 16 && pm.numel() >= B * nchunk
+                && ps.numel() >= B * nchunk, "row_topk: partials too small");
+    pp = part.data_ptr();
+    pmp = pm.data_ptr<float>();
+    psp = ps.data_ptr<float>();
+  }
+  launch_row_topk(x.data_ptr(), is_f32 ? 1 : 0, B, L, (int)k, pp, pmp, psp,
+                  vals.data_ptr<float>(), idx.data_ptr<long>(),
+                  lse.data_ptr<float>(), cur_stream());
+}
+
 void transpose_w(torch::Tensor w, torch::Tensor wt) {
   CHK_CUDA(w); CHK_CONTIG(w); CHK_DT(w, torch::kBFloat16);
   CHK_CONTIG(wt); CHK_DT(wt, torch::kBFloat16);
@@ -853,6 +900,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("head_bwd_prep", &head_bwd_prep);
   m.def("swizzle_cv", &swizzle_cv);
   m.def("row_max_argmax", &row_max_argmax);
+  m.def("row_topk", &row_topk);
   m.def("inv_rownorm", &inv_rownorm);
   m.def("rowscale", &rowscale);
   m.def("angular_fwd", &angular_fwd);

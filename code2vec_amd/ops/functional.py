@@ -851,6 +851,52 @@ def row_max_argmax(logits: torch.Tensor):
     return torch.max(logits.float(), dim=1)
 
 
+# chunk width of the K19 stage-1 grid (columns per block); the extension
+# checks it against the compiled value.  Exposed so tests can plant values
+# on chunk boundaries.
+ROW_TOPK_CHUNK = 32768
+_ROW_TOPK_SLOTS = 16  # candidates each chunk hands to stage 2
+
+
+def row_topk(x: torch.Tensor, k: int):
+    """K19: per-row top-k (1 <= k <= 16) + log-sum-exp in one pass.
+
+    Returns (vals f32 [B, k], idx i64 [B, k], lse f32 [B]) in the total
+    order of ops/reference.py::row_topk (descending value, ties to the
+    smallest column).  Device bf16/f32 input runs the HIP kernel (no host
+    sync; capturable); CPU tensors and other dtypes take the reference.
+    A non-contiguous device tensor is an error rather than a silent copy
+    or an eager fallback."""
+    from . import reference as R
+
+    k = int(k)
+    R.check_row_topk_args(x, k)
+    if not (x.is_cuda and x.dtype in (torch.bfloat16, torch.float32)):
+        return R.row_topk(x, k)
+    if not x.is_contiguous():
+        raise ValueError("row_topk: device input must be contiguous")
+    B, L = x.shape
+    dev = x.device
+    vals = torch.empty(B, k, dtype=torch.float32, device=dev)
+    idx = torch.empty(B, k, dtype=torch.int64, device=dev)
+    lse = torch.empty(B, dtype=torch.float32, device=dev)
+    nchunk = (L + ROW_TOPK_CHUNK - 1) // ROW_TOPK_CHUNK
+    if nchunk > 1:
+        part = torch.empty(B, nchunk, _ROW_TOPK_SLOTS, dtype=torch.int64,
+                           device=dev)
+        pm = torch.empty(B, nchunk, dtype=torch.float32, device=dev)
+        ps = torch.empty_like(pm)
+    else:
+        part = pm = ps = _NONE_T
+    ext().row_topk(x, k, ROW_TOPK_CHUNK, part, pm, ps, vals, idx, lse)
+    return vals, idx, lse
+
+
+def topk_probs(vals: torch.Tensor, lse: torch.Tensor) -> torch.Tensor:
+    """Softmax probabilities of row_topk's selected entries."""
+    return torch.exp(vals - lse[:, None])
+
+
 def adam_step(
     param: torch.Tensor,
     grad: torch.Tensor,

@@ -89,6 +89,36 @@ def angular_margin_head(cv, weight, label, cos_m, sin_m, inverse_temp):
     return outputs * inverse_temp
 
 
+ROW_TOPK_MAX_K = 16
+
+
+def check_row_topk_args(x, k: int) -> None:
+    """Argument contract shared by the oracle and the HIP op."""
+    if x.dim() != 2:
+        raise ValueError(f"row_topk: x must be [B, L], got {tuple(x.shape)}")
+    if not 1 <= k <= ROW_TOPK_MAX_K:
+        raise ValueError(
+            f"row_topk: k must be in 1..{ROW_TOPK_MAX_K}, got {k}")
+    if k > x.shape[1]:
+        raise ValueError(
+            f"row_topk: k = {k} exceeds row length {x.shape[1]}")
+
+
+def row_topk(x, k: int):
+    """K19: per-row top-k + log-sum-exp.
+
+    Total order: descending value, ties to the smallest column (a stable
+    descending sort) — ``torch.topk`` does not promise this.  Returns
+    (vals f32 [B, k], idx i64 [B, k], lse f32 [B]); lse runs over the whole
+    row, so ``exp(vals - lse[:, None])`` are softmax probabilities.
+    """
+    check_row_topk_args(x, k)
+    xf = x.float()
+    vals, idx = torch.sort(xf, dim=1, descending=True, stable=True)
+    return (vals[:, :k].contiguous(), idx[:, :k].contiguous(),
+            torch.logsumexp(xf, dim=1))
+
+
 def logsoftmax_nll(logits, label, weight):
     """K12: log_softmax + weighted NLL (reference main.py:251-264 with the
     criterion built at main.py:129-130).

@@ -4,6 +4,8 @@
 Times each framework op at the top11 flagship shape; variants switch via
 env vars read by ops/functional.py.  Usage (on a GPU box):
     python tools/kbench.py [op ...]
+``row_topk`` (K19 vs torch.topk + torch.logsumexp) is not in the default
+set; asked for alone it skips building the model-shaped operands.
 """
 
 from __future__ import annotations
@@ -33,6 +35,46 @@ def timeit(fn, iters=30, warmup=5):
     return start.elapsed_time(end) / iters * 1000  # us
 
 
+def bench_row_topk(dev, results, rounds=5):
+    """K19 row_topk vs the stock torch.topk + torch.logsumexp pair on the
+    SAME tensor, alternating the two within each round (median / min over
+    rounds).  Shapes: the prediction head at B = 1024, k = 10 for each L
+    in C2V_KBENCH_TOPK_L (bf16 logits), plus the attention shape
+    (1024, 200) fp32."""
+    B, k = 1024, 10
+    Ls = [int(v) for v in os.environ.get(
+        "C2V_KBENCH_TOPK_L", "72416,261245").split(",")]
+    g = torch.Generator(device=dev).manual_seed(0)
+    shapes = [(L, torch.bfloat16) for L in Ls] + [(200, torch.float32)]
+    for L, dtype in shapes:
+        x = torch.randn(B, L, generator=g, device=dev)
+        if dtype == torch.float32:
+            x = torch.softmax(x, dim=1)
+        x = x.to(dtype).contiguous()
+        tag = f"L={L},{'bf16' if dtype == torch.bfloat16 else 'f32'}"
+
+        def ours():
+            return Fn.row_topk(x, k)
+
+        def pair():
+            return torch.topk(x, k, dim=1), torch.logsumexp(x, dim=1)
+
+        iters = 20 if L > 1000 else 200
+        t_ours, t_pair = [], []
+        for _ in range(rounds):
+            t_ours.append(timeit(ours, iters=iters))
+            t_pair.append(timeit(pair, iters=iters))
+        t_ours.sort()
+        t_pair.sort()
+        results[f"row_topk({tag}) med"] = t_ours[rounds // 2]
+        results[f"row_topk({tag}) min"] = t_ours[0]
+        results[f"topk+lse({tag}) med"] = t_pair[rounds // 2]
+        results[f"topk+lse({tag}) min"] = t_pair[0]
+        gbs = x.numel() * x.element_size() / (t_ours[rounds // 2] * 1e-6) / 1e9
+        print(f"# row_topk {tag}: {gbs:.0f} GB/s of input read (median)")
+        del x
+
+
 def main():
     if "--help" in sys.argv or "-h" in sys.argv:
         print(__doc__.strip())
@@ -41,6 +83,13 @@ def main():
         print("kbench: needs a GPU (per-kernel timing); run under gpurun")
         return
     dev = torch.device("cuda:0")
+    if sys.argv[1:] == ["row_topk"]:
+        # needs none of the model-shaped operands built below
+        results = {}
+        bench_row_topk(dev, results)
+        for k, vv in results.items():
+            print(f"{k:32s} {vv:10.1f} us")
+        return
     B, C = 1024, 200
     T, P, L = 360632, 342846, 30000
     L = int(os.environ.get("C2V_KBENCH_L", L))  # e.g. 261000 (java-large)
@@ -228,6 +277,9 @@ def main():
         results["head_bwd_dcv_rc"] = timeit(
             lambda: ext().head_bwd_dcv_rc(cvimg_a, wimg_a, wimg, coef_lse,
                                           partials, B, L, chunk))
+
+    if "row_topk" in ops:
+        bench_row_topk(dev, results)
 
     for k, vv in results.items():
         print(f"{k:24s} {vv:10.1f} us")
