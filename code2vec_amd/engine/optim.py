@@ -103,6 +103,20 @@ class FusedAdam:
             self.eps, self.weight_decay,
         )
 
+    @torch.no_grad()
+    def step_table_deferred(self, p, record) -> None:
+        """Adam on a whole bf16 embedding table whose gradient arrives as
+        a ``DeferredTableGrad`` record (no dense gradient table exists):
+        the kernel gathers each row's contributions itself.  Same step
+        count as the enclosing ``step()`` call, same result as
+        ``step_rows`` on the materialized gradient."""
+        st = self.state[p]
+        Fn.table_adam_deferred(
+            p.data, st["master"], st["m"], st["v"], record,
+            self.bc_pow, self.lr, self.beta1, self.beta2,
+            self.eps, self.weight_decay,
+        )
+
     def zero_grad(self, set_to_none: bool = False) -> None:
         # NOTE: when grads are BucketedAllReduce views, use ddp.zero_grad()
         # instead — set_to_none=True here would detach the bucket views.

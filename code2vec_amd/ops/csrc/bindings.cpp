@@ -22,6 +22,13 @@ void launch_gather_concat_bwd(const int*, const int*, const int*, const void*,
 void launch_embed_scatter_sorted(const int*, const long*, const void*, float*,
                                  void*, unsigned char*, long, long, int, int,
                                  int, int, int, hipStream_t);
+void launch_embed_scatter_heavy(const int*, const long*, const int*,
+                                const void*, float*, long, long, int, int,
+                                int, int, int, hipStream_t);
+void launch_adam_table_bf16(void*, const void*, const long*, int*, const int*,
+                            float*, float*, float*, float*, long, int, long,
+                            long, long, int, int, int, int, const double*,
+                            float, float, float, float, float, hipStream_t);
 void launch_count_indices(const int*, int*, long, hipStream_t);
 void launch_cast_clear_rows(float*, const int*, unsigned char*, void*, long,
                             int, hipStream_t);
@@ -827,6 +834,87 @@ void adam_step_bf16(torch::Tensor p, torch::Tensor g, torch::Tensor master,
                    (float)b2, (float)eps, (float)wd, cur_stream());
 }
 
+// Shared shape checks of the deferred table-gradient record: N sorted
+// entries (N == M, or 2M with two column offsets) over gout [M, KP].
+static void check_table_record(const torch::Tensor& perm,
+                               const torch::Tensor& counts,
+                               const torch::Tensor& gout, long T, int S,
+                               int64_t M, int64_t KP, int64_t off0,
+                               int64_t off1) {
+  CHK_CUDA(gout); CHK_CONTIG(gout); CHK_DT(gout, torch::kBFloat16);
+  CHK_CONTIG(perm); CHK_DT(perm, torch::kInt64);
+  CHK_CONTIG(counts); CHK_DT(counts, torch::kInt32);
+  const long N = perm.numel();
+  TORCH_CHECK(M > 0 && (N == M || N == 2 * M), "record: N must be M or 2M");
+  TORCH_CHECK(gout.numel() >= M * KP, "record: gout smaller than [M, KP]");
+  TORCH_CHECK(off0 >= 0 && off1 >= 0 && off0 + S <= KP && off1 + S <= KP,
+              "record: column window outside gout");
+  TORCH_CHECK(counts.numel() >= T + 1, "record: counts shorter than T + 1");
+}
+
+// Heavy-row pre-pass of adam_table_bf16: rows with counts > thr are
+// reduced into the persistent fp32 scratch `dtable` [T, S].
+void embed_scatter_heavy(torch::Tensor sorted_idx, torch::Tensor perm,
+                         torch::Tensor counts, torch::Tensor gout,
+                         torch::Tensor dtable, int64_t M, int64_t KP,
+                         int64_t off0, int64_t off1, int64_t thr) {
+  CHK_CUDA(sorted_idx); CHK_CONTIG(sorted_idx);
+  CHK_DT(sorted_idx, torch::kInt32);
+  CHK_DT(dtable, torch::kFloat32); CHK_CONTIG(dtable);
+  TORCH_CHECK(dtable.dim() == 2, "dtable must be [T, S]");
+  const long T = dtable.size(0);
+  const int S = dtable.size(1);
+  check_table_record(perm, counts, gout, T, S, M, KP, off0, off1);
+  TORCH_CHECK(sorted_idx.numel() == perm.numel(), "sorted_idx/perm sizes");
+  TORCH_CHECK(S % 2 == 0 && S <= 512 && KP % 2 == 0 && off0 % 2 == 0 &&
+                  off1 % 2 == 0, "embed_scatter_heavy: S/KP/offset alignment");
+  TORCH_CHECK(thr >= 32, "embed_scatter_heavy: thr must be >= 32");
+  launch_embed_scatter_heavy(sorted_idx.data_ptr<int>(),
+                             perm.data_ptr<long>(), counts.data_ptr<int>(),
+                             gout.data_ptr(), dtable.data_ptr<float>(),
+                             perm.numel(), M, (int)KP, S, (int)off0,
+                             (int)off1, (int)thr, cur_stream());
+}
+
+// Row-gathering table Adam: p bf16 [T, S] updated from the deferred record
+// (gout, perm, counts, cursor) instead of a dense gradient; consumes
+// counts (left all-zero) and the heavy rows of `scratch` (re-zeroed).
+void adam_table_bf16(torch::Tensor p, torch::Tensor gout, torch::Tensor perm,
+                     torch::Tensor counts, torch::Tensor cursor,
+                     torch::Tensor scratch, torch::Tensor master,
+                     torch::Tensor m, torch::Tensor v, torch::Tensor bc_pow,
+                     int64_t M, int64_t KP, int64_t off0, int64_t off1,
+                     int64_t thr, double lr, double b1, double b2, double eps,
+                     double wd) {
+  CHK_CUDA(p); CHK_CONTIG(p); CHK_DT(p, torch::kBFloat16);
+  TORCH_CHECK(p.dim() == 2, "p must be [T, S]");
+  const long T = p.size(0);
+  const int S = p.size(1);
+  check_table_record(perm, counts, gout, T, S, M, KP, off0, off1);
+  CHK_CONTIG(cursor); CHK_DT(cursor, torch::kInt32);
+  TORCH_CHECK(cursor.numel() >= T, "cursor shorter than T");
+  CHK_DT(scratch, torch::kFloat32); CHK_CONTIG(scratch);
+  CHK_DT(master, torch::kFloat32); CHK_CONTIG(master);
+  CHK_DT(m, torch::kFloat32); CHK_CONTIG(m);
+  CHK_DT(v, torch::kFloat32); CHK_CONTIG(v);
+  CHK_DT(bc_pow, torch::kFloat64);
+  const long n = T * S;
+  TORCH_CHECK(scratch.numel() == n && master.numel() == n &&
+                  m.numel() == n && v.numel() == n, "state sizes");
+  TORCH_CHECK(S % 4 == 0 && KP % 4 == 0 && off0 % 4 == 0 && off1 % 4 == 0,
+              "adam_table_bf16: S, KP and offsets must be multiples of 4");
+  TORCH_CHECK(n / 4 < (1L << 32), "adam_table_bf16: table too large");
+  TORCH_CHECK(thr >= 32, "adam_table_bf16: thr must be >= 32");
+  launch_adam_table_bf16(
+      p.data_ptr(), gout.data_ptr(), perm.data_ptr<long>(),
+      counts.data_ptr<int>(), cursor.data_ptr<int>(),
+      scratch.data_ptr<float>(), master.data_ptr<float>(),
+      m.data_ptr<float>(), v.data_ptr<float>(), T, S, counts.numel(),
+      perm.numel(), M, (int)KP, (int)off0, (int)off1, (int)thr,
+      (const double*)bc_pow.data_ptr(), (float)lr, (float)b1, (float)b2,
+      (float)eps, (float)wd, cur_stream());
+}
+
 void adam_step_f32(torch::Tensor p, torch::Tensor g, torch::Tensor m,
                    torch::Tensor v, torch::Tensor bc_pow, double lr,
                    double b1, double b2, double eps, double wd) {
@@ -917,5 +1005,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adam_tick", &adam_tick);
   m.def("adam_step_bf16", &adam_step_bf16);
   m.def("adam_step_f32", &adam_step_f32);
+  m.def("embed_scatter_heavy", &embed_scatter_heavy);
+  m.def("adam_table_bf16", &adam_table_bf16);
   m.def("adam_step_f32_multi", &adam_step_f32_multi);
 }

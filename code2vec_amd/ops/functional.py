@@ -74,6 +74,15 @@ _NONE_T = torch.Tensor()  # "not provided" sentinel for optional kernel args
 # (the other table's sort/scatter chain) still runs.
 EARLY_GRAD_CALLBACKS = {}
 OWNED_GRAD_KEYS = set()
+# Deferred table gradients (single-GPU fused step): for an owned key also
+# listed here the backward runs ONLY the counting sort and hands the owner
+# a DeferredTableGrad record instead of a dense bf16 table; the optimizer's
+# row-gathering table Adam (adam_table_bf16) rebuilds each row's gradient
+# from the record.  C2V_FUSED_TABLE_ADAM=0 is the A/B switch (read by
+# parallel/ddp.py); C2V_TABLE_ADAM_HEAVY is the run length above which a
+# row is pre-reduced into the fp32 scratch instead of gathered in-kernel.
+DEFERRED_GRAD_KEYS = set()
+_TABLE_ADAM_HEAVY = int(os.environ.get("C2V_TABLE_ADAM_HEAVY", "64"))
 
 from . import ext, round_up
 
@@ -139,45 +148,125 @@ def _scatter_embedding_grads(starts, paths, ends, gout, term_shape,
     dense embedding grads.  Counting-sort groups the index lists; run-owner
     waves write interior rows' bf16 grads directly; boundary-crossing runs
     (heavy hitters) combine via flagged persistent fp32 scratch in
-    cast_clear_rows (which also re-zeroes what it consumed)."""
-    dev = gout.device
+    cast_clear_rows (which also re-zeroes what it consumed).
+
+    Deferred form: for an owned key listed in DEFERRED_GRAD_KEYS only the
+    grouping runs; the owner's callback gets a DeferredTableGrad record and
+    autograd gets None (see table_adam_deferred)."""
     M = starts.numel()
     TS, PS = term_shape[1], path_shape[1]
     KP = gout.shape[1]
-    dterm32 = _scratch_f32("term", term_shape, dev)
-    dpath32 = _scratch_f32("path", path_shape, dev)
-    flags_t = _scratch_flags("term", term_shape[0], dev)
-    flags_p = _scratch_flags("path", path_shape[0], dev)
-    dterm = torch.empty(term_shape, dtype=torch.bfloat16, device=dev)
-    dpath = torch.empty(path_shape, dtype=torch.bfloat16, device=dev)
+
+    def one_table(tag, idx, shape, key, off0, off1):
+        sorted_idx, perm, counts, cursor = _group_by_index(
+            idx, shape[0], pool_tag=tag, with_cursor=True)
+        rec = DeferredTableGrad(tag, gout, perm, counts, cursor, sorted_idx,
+                                M, KP, off0, off1, tuple(shape))
+        cb = EARLY_GRAD_CALLBACKS.get(key) if key is not None else None
+        if (cb is not None and key in OWNED_GRAD_KEYS
+                and key in DEFERRED_GRAD_KEYS):
+            # deferred: the owner's optimizer step consumes the record
+            _PENDING_DEFERRED[counts.data_ptr()] = rec
+            cb(rec)
+            return None
+        grad = materialize_deferred(rec)
+        if cb is not None:
+            cb(grad)
+        # the callback owner keeps the buffer; autograd must not adopt
+        # (or clone) it
+        return None if key in OWNED_GRAD_KEYS else grad
+
     # term's FULL chain (sort+scatter+cast) runs before path's STARTS, so
     # the early callback can put term's all-reduce on the wire while
     # path's ~100 us of scatter kernels still execute (DP overlap)
     idx_se = torch.cat([starts.view(-1), ends.view(-1)])
-    sorted_se, perm_se, counts_se = _group_by_index(idx_se, term_shape[0],
-                                                    pool_tag="term")
-    ext().embed_scatter_sorted(sorted_se, perm_se, gout, dterm32, dterm,
-                               flags_t, M, KP, 0, TS + PS, _SCATTER_R)
-    ext().cast_clear_rows(dterm32, counts_se, flags_t, dterm)
-    if term_key is not None:
-        cb = EARLY_GRAD_CALLBACKS.get(term_key)
-        if cb is not None:
-            cb(dterm)
-    sorted_p, perm_p, counts_p = _group_by_index(paths.view(-1),
-                                                 path_shape[0],
-                                                 pool_tag="path")
-    ext().embed_scatter_sorted(sorted_p, perm_p, gout, dpath32, dpath,
-                               flags_p, M, KP, TS, TS, _SCATTER_R)
-    ext().cast_clear_rows(dpath32, counts_p, flags_p, dpath)
-    if path_key is not None:
-        cb = EARLY_GRAD_CALLBACKS.get(path_key)
-        if cb is not None:
-            cb(dpath)
-    if term_key in OWNED_GRAD_KEYS:
-        dterm = None  # the callback owner keeps the buffer; autograd must
-    if path_key in OWNED_GRAD_KEYS:  # not adopt (or clone) it
-        dpath = None
+    dterm = one_table("term", idx_se, term_shape, term_key, 0, TS + PS)
+    dpath = one_table("path", paths.view(-1), path_shape, path_key, TS, TS)
     return dterm, dpath
+
+
+class DeferredTableGrad:
+    """One embedding table's gradient as the counting sort left it: the
+    sorted run of row r is [cursor[r] - counts[r], cursor[r]) and entry k
+    of it is gout row perm[k] (o < M at column off0, else row o - M at
+    off1).  ``counts`` is the persistent histogram, so exactly one of
+    table_adam_deferred / materialize_deferred / discard_deferred must
+    consume the record before the next backward regroups that table;
+    ``gout`` stays alive through the record until then."""
+
+    __slots__ = ("tag", "gout", "perm", "counts", "cursor", "sorted_idx",
+                 "M", "KP", "off0", "off1", "shape", "consumed")
+
+    def __init__(self, tag, gout, perm, counts, cursor, sorted_idx, M, KP,
+                 off0, off1, shape):
+        self.tag, self.gout, self.perm = tag, gout, perm
+        self.counts, self.cursor, self.sorted_idx = counts, cursor, sorted_idx
+        self.M, self.KP, self.off0, self.off1 = M, KP, off0, off1
+        self.shape = shape
+        self.consumed = False
+
+    def _consume(self):
+        if self.consumed:
+            raise RuntimeError("deferred table gradient consumed twice")
+        self.consumed = True
+        key = self.counts.data_ptr()
+        if _PENDING_DEFERRED.get(key) is self:
+            del _PENDING_DEFERRED[key]
+
+    def _release(self):
+        self.gout = self.perm = self.sorted_idx = None
+
+
+# counts buffer address -> record handed out and not yet consumed (the
+# histogram it describes is still in that buffer)
+_PENDING_DEFERRED = {}
+
+
+def materialize_deferred(rec: DeferredTableGrad) -> torch.Tensor:
+    """Dense bf16 gradient table from a record: the sorted scatter plus
+    cast_clear_rows (which consumes counts/flags and re-zeroes the fp32
+    scratch rows it read)."""
+    rec._consume()
+    dev = rec.gout.device
+    d32 = _scratch_f32(rec.tag, rec.shape, dev)
+    flags = _scratch_flags(rec.tag, rec.shape[0], dev)
+    grad = torch.empty(rec.shape, dtype=torch.bfloat16, device=dev)
+    ext().embed_scatter_sorted(rec.sorted_idx, rec.perm, rec.gout, d32, grad,
+                               flags, rec.M, rec.KP, rec.off0, rec.off1,
+                               _SCATTER_R)
+    ext().cast_clear_rows(d32, rec.counts, flags, grad)
+    rec._release()
+    return grad
+
+
+def discard_deferred(rec: DeferredTableGrad) -> None:
+    """Drop an unconsumed record (a backward with no optimizer step).  Only
+    the histogram was written so far: flags and the fp32 scratch are still
+    all-zero, so re-zeroing counts restores every invariant."""
+    if rec.consumed:
+        return
+    rec._consume()
+    rec.counts.zero_()
+    rec._release()
+
+
+def table_adam_deferred(param, master, m, v, rec: DeferredTableGrad, bc_pow,
+                        lr, beta1, beta2, eps, weight_decay) -> None:
+    """K16b: Adam on a whole bf16 table straight from a deferred record —
+    heavy rows pre-reduced into the fp32 scratch, every other row's
+    gradient gathered inside the Adam kernel.  Leaves counts and the
+    scratch all-zero (flags are never set on this path)."""
+    rec._consume()
+    assert tuple(param.shape) == rec.shape and master is not None
+    scratch = _scratch_f32(rec.tag, rec.shape, param.device)
+    ext().embed_scatter_heavy(rec.sorted_idx, rec.perm, rec.counts, rec.gout,
+                              scratch, rec.M, rec.KP, rec.off0, rec.off1,
+                              _TABLE_ADAM_HEAVY)
+    ext().adam_table_bf16(param, rec.gout, rec.perm, rec.counts, rec.cursor,
+                          scratch, master, m, v, bc_pow, rec.M, rec.KP,
+                          rec.off0, rec.off1, _TABLE_ADAM_HEAVY, lr, beta1,
+                          beta2, eps, weight_decay)
+    rec._release()
 
 
 _scratch_cache = {}
@@ -263,22 +352,30 @@ def _slab_sum(p: torch.Tensor) -> torch.Tensor:
 
 
 def _group_by_index(idx: torch.Tensor, table_rows: int,
-                    pool_tag: Optional[str] = None):
+                    pool_tag: Optional[str] = None,
+                    with_cursor: bool = False):
     """Counting sort: returns (sorted_idx i32, perm i64, counts i32)
-    grouping equal indexes contiguously (ascending).
+    grouping equal indexes contiguously (ascending); ``with_cursor`` also
+    returns the cursor, which scatter_group leaves at each run's END.
 
     With ``pool_tag`` (the training hot path) the histogram lives in a
     PERSISTENT all-zero buffer whose invariant cast_clear_rows restores
     by consuming the counts it reads, and the cursor comes from the
     custom 3-kernel exclusive scan — this removes two torch.zeros fills
     and a rocprim lookback scan (+init) per table per step (~21 us each).
-    Callers that do NOT route the counts through cast_clear_rows must use
-    the default (fresh-buffer) form.
+    Callers that do NOT route the counts through cast_clear_rows (or the
+    table Adam, which clears them too) must use the default (fresh-buffer)
+    form.
     """
     N = idx.numel()
     dev = idx.device
     if pool_tag is not None:
         counts = _scratch_i32(f"counts_{pool_tag}", table_rows + 1, dev)
+        # a deferred record nobody consumed (backward without a step)
+        # still holds its histogram in this buffer
+        stale = _PENDING_DEFERRED.get(counts.data_ptr())
+        if stale is not None:
+            discard_deferred(stale)
         cursor = _scratch_i32(f"cursor_{pool_tag}", table_rows + 1, dev,
                               zero=False)
         spart = _scratch_i32(f"scanp_{pool_tag}",
@@ -306,6 +403,8 @@ def _group_by_index(idx: torch.Tensor, table_rows: int,
     sorted_idx = torch.empty(N, dtype=torch.int32, device=dev)
     perm = torch.empty(N, dtype=torch.int64, device=dev)
     ext().group_by_index(idx, counts, cursor, sorted_idx, perm, False)
+    if with_cursor:
+        return sorted_idx, perm, counts, cursor
     return sorted_idx, perm, counts
 
 

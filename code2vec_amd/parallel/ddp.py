@@ -12,6 +12,12 @@ Three modes per parameter:
   waits chunk-by-chunk and runs the fused-Adam row update for each chunk
   while later chunks are still on the wire — the table optimizer work
   (the largest Adam cost) hides most of the exposed all-reduce tail.
+  Without communication (world_size == 1) nothing needs the dense table
+  at all: with ``fuse_owned_step`` the backward only groups the indices
+  and hands over a ``Fn.DeferredTableGrad`` record, and
+  ``finish_and_step`` runs ``optim.step_table_deferred`` — a table Adam
+  that gathers each row's gradient itself.  ``finish()`` still publishes
+  a dense ``p.grad`` by materializing the record.
 - DIRECT (>= direct_threshold bytes — e.g. the output head): the
   parameter's grad tensor is all-reduced in place as soon as its
   post-accumulate hook fires.  p.grad stays None between steps
@@ -29,6 +35,7 @@ model in PERF.md §DP.
 
 from __future__ import annotations
 
+import os
 from typing import List, Optional
 
 import torch
@@ -67,10 +74,17 @@ class BucketedAllReduce:
         enabled: Optional[bool] = None,
         owned_params: Optional[List[torch.nn.Parameter]] = None,
         owned_chunks: int = 4,
+        fuse_owned_step: Optional[bool] = None,
     ) -> None:
         self.world_size = world_size
         self.group = process_group
         self.enabled = enabled if enabled is not None else world_size > 1
+        # deferred table gradients + row-gathering table Adam: only without
+        # communication (an all-reduce needs the dense table), default on
+        # there unless C2V_FUSED_TABLE_ADAM=0
+        if fuse_owned_step is None:
+            fuse_owned_step = os.environ.get("C2V_FUSED_TABLE_ADAM", "1") != "0"
+        self.fuse_owned_step = bool(fuse_owned_step) and not self.enabled
         self.params = [p for p in params if p.requires_grad]
         self.owned_chunks = owned_chunks
 
@@ -86,6 +100,11 @@ class BucketedAllReduce:
             key = p.data_ptr()
             Fn.OWNED_GRAD_KEYS.add(key)
             Fn.EARLY_GRAD_CALLBACKS[key] = self._make_owned_cb(p)
+            if (self.fuse_owned_step and p.is_cuda and p.dim() == 2
+                    and p.dtype == torch.bfloat16 and p.shape[1] % 4 == 0):
+                Fn.DEFERRED_GRAD_KEYS.add(key)
+            else:
+                Fn.DEFERRED_GRAD_KEYS.discard(key)
 
         self.direct_params = [
             p for p in rest
@@ -135,6 +154,8 @@ class BucketedAllReduce:
     # ------------------------------------------------------------------
     def _make_owned_cb(self, p):
         def cb(grad):
+            # ``grad`` is the dense table, or (deferred keys only, never
+            # with communication enabled) a Fn.DeferredTableGrad record
             entry = {"grad": grad, "handles": []}
             if self.enabled:
                 rows = grad.shape[0]
@@ -155,6 +176,11 @@ class BucketedAllReduce:
             b.pending = len(b.params)
             b.handle = None
         self._direct_handles = []
+        # a deferred record nobody consumed (backward without a step) still
+        # holds the table's histogram: drop it, restoring the invariants
+        for entry in getattr(self, "_owned_state", {}).values():
+            if isinstance(entry["grad"], Fn.DeferredTableGrad):
+                Fn.discard_deferred(entry["grad"])
         self._owned_state = {}
         self._owned_order = []
 
@@ -215,6 +241,8 @@ class BucketedAllReduce:
             for h, view in entry["handles"]:
                 h.wait()
                 view.div_(self.world_size)
+            if isinstance(entry["grad"], Fn.DeferredTableGrad):
+                entry["grad"] = Fn.materialize_deferred(entry["grad"])
             p.grad = entry["grad"]
         self._reset_pending_comm()
 
@@ -230,6 +258,14 @@ class BucketedAllReduce:
         for p in self._owned_order:
             entry = self._owned_state[id(p)]
             grad = entry["grad"]
+            if grad is None:  # deferred record already consumed
+                continue
+            if isinstance(grad, Fn.DeferredTableGrad):
+                if hasattr(optim, "step_table_deferred"):
+                    optim.step_table_deferred(p, grad)
+                    entry["grad"] = None
+                    continue
+                grad = entry["grad"] = Fn.materialize_deferred(grad)
             if entry["handles"]:
                 row0 = 0
                 for h, view in entry["handles"]:
@@ -268,4 +304,5 @@ class BucketedAllReduce:
         for p in self.owned_params:
             key = p.data_ptr()
             Fn.OWNED_GRAD_KEYS.discard(key)
+            Fn.DEFERRED_GRAD_KEYS.discard(key)
             Fn.EARLY_GRAD_CALLBACKS.pop(key, None)

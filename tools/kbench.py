@@ -4,8 +4,10 @@
 Times each framework op at the top11 flagship shape; variants switch via
 env vars read by ops/functional.py.  Usage (on a GPU box):
     python tools/kbench.py [op ...]
-``row_topk`` (K19 vs torch.topk + torch.logsumexp) is not in the default
-set; asked for alone it skips building the model-shaped operands.
+``row_topk`` (K19 vs torch.topk + torch.logsumexp) and ``table_adam``
+(scatter + cast_clear + adam_bf16 vs the row-gathering table Adam) are not
+in the default set; asked for alone they skip building the model-shaped
+operands.
 """
 
 from __future__ import annotations
@@ -75,6 +77,73 @@ def bench_row_topk(dev, results, rounds=5):
         del x
 
 
+def bench_table_adam(dev, results, rounds=5):
+    """Table optimizer step from one grouped gradient, old against new on
+    the SAME buffers, alternating within each round (median / min):
+      old: embed_scatter_sorted + cast_clear_rows + adam_step_bf16
+      new: embed_scatter_heavy + adam_table_bf16 (+ its counts clear)
+    at the top11 table shapes (term: 2M entries, two offsets; path: M
+    entries) with uniform indices over [1, rows).  The counting sort runs
+    once outside the timed region; each timed call first restores the
+    histogram it consumes (a 1.4-MB copy, in both variants)."""
+    from code2vec_amd.ops import ext
+
+    S, KP, M = 104, 320, 1024 * 200  # M = B * C contexts
+    thr = Fn._TABLE_ADAM_HEAVY
+    g = torch.Generator(device=dev).manual_seed(0)
+    gout = torch.randn(M, KP, generator=g, device=dev).to(torch.bfloat16)
+    for tag, T, N, off0, off1 in (("term", 360632, 2 * M, 0, 2 * S),
+                                  ("path", 342846, M, S, S)):
+        idx = torch.randint(1, T, (N,), generator=g, device=dev,
+                            dtype=torch.int32)
+        sorted_idx, perm, counts0, cursor = Fn._group_by_index(
+            idx, T, with_cursor=True)
+        counts = counts0.clone()
+        p = (torch.randn(T, S, generator=g, device=dev) * 0.1).to(
+            torch.bfloat16)
+        master = p.float().view(-1).clone()
+        m = torch.zeros(T * S, device=dev)
+        v = torch.zeros(T * S, device=dev)
+        scratch = torch.zeros(T, S, device=dev)
+        flags = torch.zeros(T, dtype=torch.uint8, device=dev)
+        dense = torch.empty(T, S, dtype=torch.bfloat16, device=dev)
+        bc_pow = torch.full((2,), 0.5, dtype=torch.float64, device=dev)
+        hp = (0.01, 0.9, 0.999, 1e-8, 0.0)
+
+        def old():
+            counts.copy_(counts0)
+            ext().embed_scatter_sorted(sorted_idx, perm, gout, scratch,
+                                       dense, flags, M, KP, off0, off1, 16)
+            ext().cast_clear_rows(scratch, counts, flags, dense)
+            Fn.adam_step(p, dense, master, m, v, bc_pow, *hp)
+
+        def new():
+            counts.copy_(counts0)
+            ext().embed_scatter_heavy(sorted_idx, perm, counts, gout,
+                                      scratch, M, KP, off0, off1, thr)
+            ext().adam_table_bf16(p, gout, perm, counts, cursor, scratch,
+                                  master, m, v, bc_pow, M, KP, off0, off1,
+                                  thr, *hp)
+
+        def dense_only():  # the streaming floor the new kernel is set against
+            Fn.adam_step(p, dense, master, m, v, bc_pow, *hp)
+
+        t = {"old": [], "new": [], "adam_bf16 alone": []}
+        for _ in range(rounds):
+            t["old"].append(timeit(old, iters=20))
+            t["new"].append(timeit(new, iters=20))
+            t["adam_bf16 alone"].append(timeit(dense_only, iters=20))
+        for name, vals in t.items():
+            vals.sort()
+            results[f"table_adam({tag}) {name} med"] = vals[rounds // 2]
+            results[f"table_adam({tag}) {name} min"] = vals[0]
+        # bytes the new path has to move: 28 B/param of state traffic,
+        # the gathered gradient rows, and the run metadata
+        nbytes = T * S * 28 + N * S * 2 + N * 8 + (T + 1) * 12
+        gbs = nbytes / (t["new"][rounds // 2] * 1e-6) / 1e9
+        print(f"# table_adam {tag}: {gbs:.0f} GB/s effective (median, new)")
+
+
 def main():
     if "--help" in sys.argv or "-h" in sys.argv:
         print(__doc__.strip())
@@ -83,12 +152,15 @@ def main():
         print("kbench: needs a GPU (per-kernel timing); run under gpurun")
         return
     dev = torch.device("cuda:0")
-    if sys.argv[1:] == ["row_topk"]:
+    if sys.argv[1:] in (["row_topk"], ["table_adam"]):
         # needs none of the model-shaped operands built below
         results = {}
-        bench_row_topk(dev, results)
+        if sys.argv[1] == "row_topk":
+            bench_row_topk(dev, results)
+        else:
+            bench_table_adam(dev, results)
         for k, vv in results.items():
-            print(f"{k:32s} {vv:10.1f} us")
+            print(f"{k:40s} {vv:10.1f} us")
         return
     B, C = 1024, 200
     T, P, L = 360632, 342846, 30000
@@ -280,6 +352,8 @@ def main():
 
     if "row_topk" in ops:
         bench_row_topk(dev, results)
+    if "table_adam" in ops:
+        bench_table_adam(dev, results)
 
     for k, vv in results.items():
         print(f"{k:24s} {vv:10.1f} us")
