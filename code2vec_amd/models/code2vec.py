@@ -193,6 +193,7 @@ class Code2VecHIP(nn.Module):
         starts = starts.to(torch.int32)
         paths = paths.to(torch.int32)
         ends = ends.to(torch.int32)
+        x = y = cvb = None
         if Fn.FUSE_GATHER_COMBINER:
             # fused K1-K6: the concat tensor is never materialized
             y = Fn.FusedGatherCombiner.apply(
@@ -205,19 +206,31 @@ class Code2VecHIP(nn.Module):
                 starts, paths, ends, self.terminal_embedding,
                 self.path_embedding
             )
-            y = Fn.CombinerLNTanh.apply(
+        if y is None and Fn.combiner_attention_pool_supported(
+                x, self.input_weight):
+            # K3-K9 as one node: its backward never writes the attention
+            # gradient, and the forward hands back cv in bf16 as well
+            cv, attn, cvb = Fn.CombinerAttentionPool.apply(
                 x, self.input_weight, self.ln_gamma, self.ln_beta,
-                self.E, self.dropout_p, self.training,
+                self.attention_a, starts, self.E, self.dropout_p,
+                self.training,
             )
-        ccv = y.view(B, C, self.EP)
-        cv, attn = Fn.AttentionPool.apply(ccv, self.attention_a, starts, self.E)
+        else:
+            if y is None:
+                y = Fn.CombinerLNTanh.apply(
+                    x, self.input_weight, self.ln_gamma, self.ln_beta,
+                    self.E, self.dropout_p, self.training,
+                )
+            ccv = y.view(B, C, self.EP)
+            cv, attn = Fn.AttentionPool.apply(ccv, self.attention_a, starts,
+                                              self.E)
+            cvb = cv.to(torch.bfloat16)
         if opt.angular_margin_loss:
             outputs = Fn.angular_margin_head_hip(
-                cv.to(torch.bfloat16), self.output_weight, label,
+                cvb, self.output_weight, label,
                 self.cos_m, self.sin_m, opt.inverse_temp,
             )
         else:
-            cvb = cv.to(torch.bfloat16)
             if Fn.fused_head_loss_supported(cvb, self.output_weight,
                                             self.training):
                 # fused head+loss path: logits are computed WITHOUT autograd

@@ -81,7 +81,8 @@ template <bool STAGE_LDS>
 __global__ __launch_bounds__(256) void attention_fwd_kernel(
     const bf16* __restrict__ ccv, const float* __restrict__ a,
     const int* __restrict__ starts, float* __restrict__ cv,
-    float* __restrict__ attn, int B, int C, int EP, int E, int ts) {
+    bf16* __restrict__ cvb, float* __restrict__ attn, int B, int C, int EP,
+    int E, int ts) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // layout: [ccv tile (opt)] [a f32 EP] [scores C] [red 64] [partials 4*EP]
   bf16* tile = (bf16*)smem;
@@ -148,8 +149,11 @@ __global__ __launch_bounds__(256) void attention_fwd_kernel(
   }
   __syncthreads();
   for (int e = threadIdx.x; e < EP; e += blockDim.x) {
-    cv[(long)b * EP + e] = partials[e] + partials[EP + e] +
-                           partials[2 * EP + e] + partials[3 * EP + e];
+    const float s = partials[e] + partials[EP + e] + partials[2 * EP + e] +
+                    partials[3 * EP + e];
+    cv[(long)b * EP + e] = s;
+    // optional bf16 copy for the output head (saves a cast kernel)
+    if (cvb) cvb[(long)b * EP + e] = f2bf(s);
   }
   __syncthreads();  // smem reused by the next method
   }
@@ -159,13 +163,20 @@ __global__ __launch_bounds__(256) void attention_fwd_kernel(
 // Backward.  g[c] = dot(dcv, ccv[c]) (+ dattn[c]); sum_g = sum_c attn[c]*g[c];
 // ds[c] = attn[c]*(g[c]-sum_g)*mask;  dccv[c,e] = attn[c]*dcv[e] + ds[c]*a[e];
 // da[e] = sum_c ds[c]*ccv[c,e]  (per-block partials row, summed host-side).
-template <bool STAGE_LDS>
+//
+// COMPACT=1 never writes dccv: it stores ds[B*C] (fp32) instead, and the
+// combiner backward rebuilds every dccv element from attn, ds, dcv and a
+// through dccv_elem() (common.h) — the same function the dense form uses,
+// so both produce the same bits.  dcv is fp32, or bf16 when dcv_bf16 is
+// set (the output head's gradient read without a cast kernel).
+template <bool STAGE_LDS, bool COMPACT>
 __global__ __launch_bounds__(256) void attention_bwd_kernel(
-    const float* __restrict__ dcv, const float* __restrict__ dattn,
+    const void* __restrict__ dcv, const float* __restrict__ dattn,
     const bf16* __restrict__ ccv, const float* __restrict__ a,
     const int* __restrict__ starts, const float* __restrict__ attn,
-    bf16* __restrict__ dccv, float* __restrict__ da, int B, int C, int EP,
-    int E, int has_dattn, int ts) {
+    bf16* __restrict__ dccv, float* __restrict__ ds_out,
+    float* __restrict__ da, int B, int C, int EP, int E, int has_dattn,
+    int dcv_bf16, int ts) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16* tile = (bf16*)smem;
   float* lds_dcv = (float*)(smem + (STAGE_LDS ? (size_t)C * ts * 2 : 0));
@@ -179,7 +190,8 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(
   for (int b = blockIdx.x; b < B; b += gridDim.x) {
   const bf16* src = ccv + (long)b * C * EP;
   for (int e = threadIdx.x; e < EP; e += blockDim.x) {
-    lds_dcv[e] = dcv[(long)b * EP + e];
+    lds_dcv[e] = dcv_bf16 ? bf2f(((const bf16*)dcv)[(long)b * EP + e])
+                          : ((const float*)dcv)[(long)b * EP + e];
     lds_a[e] = a[e];
   }
   if (STAGE_LDS) {
@@ -222,20 +234,22 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
     const float at = attn[(long)b * C + c];
     const float mask = starts[(long)b * C + c] > 0 ? 1.0f : 0.0f;
-    ds[c] = at * (ds[c] - sum_g) * mask;
+    const float dsc = at * (ds[c] - sum_g) * mask;
+    ds[c] = dsc;
+    if (COMPACT) ds_out[(long)b * C + c] = dsc;
   }
   __syncthreads();
 
-  // phase B: dccv rows (group-per-context, coalesced bf16x8 writes) and
-  // per-lane da partial accumulators
+  // phase B: dccv rows (group-per-context, coalesced bf16x8 writes; none
+  // when COMPACT) and per-lane da partial accumulators
   // da accumulation: this lane's columns are (lane16*8 + j) + 128*i;
   // statically unrolled i (dynamic array indexing would go to scratch)
   float da_acc[3][8] = {};  // EP <= 384
   for (int c = group; c < C; c += 16) {
-    const float at = attn[(long)b * C + c];
+    const float at = COMPACT ? 0.f : attn[(long)b * C + c];
     const float dsc = ds[c];
     const bf16* row = (STAGE_LDS ? tile : src) + (long)c * rstride;
-    bf16* drow = dccv + ((long)b * C + c) * EP;
+    bf16* drow = COMPACT ? nullptr : dccv + ((long)b * C + c) * EP;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
       const int e0 = lane16 * 8 + 128 * i;
@@ -244,11 +258,12 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(
         *(uint4*)v = *(const uint4*)(row + e0);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          o[j] = f2bf(at * lds_dcv[e0 + j] + dsc * lds_a[e0 + j]);
-          da_acc[i][j] += dsc * bf2f(v[j]);
+          if (!COMPACT)
+            o[j] = dccv_elem(at, lds_dcv[e0 + j], dsc, lds_a[e0 + j]);
+          da_acc[i][j] = __builtin_fmaf(dsc, bf2f(v[j]), da_acc[i][j]);
         }
-        *(uint4*)(drow + e0) = *(uint4*)o;
-      } else if (e0 < EP) {
+        if (!COMPACT) *(uint4*)(drow + e0) = *(uint4*)o;
+      } else if (!COMPACT && e0 < EP) {
         // pad columns: dcv/a pad is zero, so the grad is exactly zero
         const uint4 z = {0, 0, 0, 0};
         *(uint4*)(drow + e0) = z;
@@ -317,39 +332,45 @@ static int attn_ts(int E, int EP) {
 }
 
 void launch_attention_fwd(const void* ccv, const float* a, const int* starts,
-                          float* cv, float* attn, int B, int C, int EP, int E,
-                          hipStream_t stream) {
+                          float* cv, void* cvb, float* attn, int B, int C,
+                          int EP, int E, hipStream_t stream) {
   const int ts = attn_ts(E, EP);
   bool stage = attn_smem(C, EP, ts, true, false) <= 160 * 1024 - 1024;
   size_t smem = attn_smem(C, EP, ts, stage, false);
   if (stage)
     attention_fwd_kernel<true>
         <<<attn_grid(attention_fwd_kernel<true>, smem, B), 256, smem,
-           stream>>>((const bf16*)ccv, a, starts, cv, attn, B, C, EP, E, ts);
+           stream>>>((const bf16*)ccv, a, starts, cv, (bf16*)cvb, attn, B, C, EP,
+                     E, ts);
   else
     attention_fwd_kernel<false>
         <<<attn_grid(attention_fwd_kernel<false>, smem, B), 256, smem,
-           stream>>>((const bf16*)ccv, a, starts, cv, attn, B, C, EP, E, ts);
+           stream>>>((const bf16*)ccv, a, starts, cv, (bf16*)cvb, attn, B, C, EP,
+                     E, ts);
 }
 
-void launch_attention_bwd(const float* dcv, const float* dattn,
+// dccv != nullptr: dense form (dccv written, ds_out unused);
+// dccv == nullptr: compact form (ds_out[B*C] written, no dccv)
+void launch_attention_bwd(const void* dcv, int dcv_bf16, const float* dattn,
                           const void* ccv, const float* a, const int* starts,
-                          const float* attn, void* dccv, float* da, int B,
-                          int C, int EP, int E, int has_dattn,
-                          hipStream_t stream) {
+                          const float* attn, void* dccv, float* ds_out,
+                          float* da, int B, int C, int EP, int E,
+                          int has_dattn, hipStream_t stream) {
   const int ts = attn_ts(E, EP);
   bool stage = attn_smem(C, EP, ts, true, true) <= 160 * 1024 - 1024;
   size_t smem = attn_smem(C, EP, ts, stage, true);
-  if (stage)
-    attention_bwd_kernel<true>
-        <<<attn_grid(attention_bwd_kernel<true>, smem, B), 256, smem,
-           stream>>>(dcv, dattn, (const bf16*)ccv, a, starts, attn,
-                     (bf16*)dccv, da, B, C, EP, E, has_dattn, ts);
-  else
-    attention_bwd_kernel<false>
-        <<<attn_grid(attention_bwd_kernel<false>, smem, B), 256, smem,
-           stream>>>(dcv, dattn, (const bf16*)ccv, a, starts, attn,
-                     (bf16*)dccv, da, B, C, EP, E, has_dattn, ts);
+#define ABWD(st, cp)                                                          \
+  attention_bwd_kernel<st, cp>                                                \
+      <<<attn_grid(attention_bwd_kernel<st, cp>, smem, B), 256, smem,         \
+         stream>>>(dcv, dattn, (const bf16*)ccv, a, starts, attn,             \
+                   (bf16*)dccv, ds_out, da, B, C, EP, E, has_dattn, dcv_bf16, \
+                   ts)
+  if (dccv) {
+    if (stage) ABWD(true, false); else ABWD(false, false);
+  } else {
+    if (stage) ABWD(true, true); else ABWD(false, true);
+  }
+#undef ABWD
 }
 
 }  // extern "C"

@@ -54,11 +54,21 @@ void launch_wgrad_gather(const int*, const int*, const int*, const void*,
 void launch_combiner_bwd(const void*, const void*, const void*, const float*,
                          const float*, const float*, const float*, void*,
                          float*, float*, long, int, int, float, hipStream_t);
+void launch_combiner_bwd_recompute(const float*, const float*, const void*,
+                                   int, const float*, int, const void*,
+                                   const void*, const float*, const float*,
+                                   const float*, const float*, void*, float*,
+                                   float*, long, int, float, hipStream_t);
 void launch_attention_fwd(const void*, const float*, const int*, float*,
-                          float*, int, int, int, int, hipStream_t);
-void launch_attention_bwd(const float*, const float*, const void*,
+                          void*, float*, int, int, int, int, hipStream_t);
+void launch_attention_bwd(const void*, int, const float*, const void*,
                           const float*, const int*, const float*, void*,
-                          float*, int, int, int, int, int, hipStream_t);
+                          float*, float*, int, int, int, int, int,
+                          hipStream_t);
+void launch_slab_sum2_f32(const float*, const float*, float*, float*, int,
+                          int, hipStream_t);
+void launch_loss_reduce(const float*, float*, float*, int, hipStream_t);
+void launch_wgrad_reduce(const float*, void*, int, int, int, hipStream_t);
 void launch_lsm_nll_fwd(const void*, const long*, const float*, float*,
                         float*, int, long, hipStream_t);
 void launch_lsm_nll_bwd(const void*, const long*, const float*, const float*,
@@ -303,9 +313,103 @@ void attention_fwd(torch::Tensor ccv, torch::Tensor a, torch::Tensor starts,
   CHK_DT(attn, torch::kFloat32); CHK_DT(starts, torch::kInt32);
   const int B = ccv.size(0), C = ccv.size(1), EP = ccv.size(2);
   launch_attention_fwd(ccv.data_ptr(), a.data_ptr<float>(),
-                       starts.data_ptr<int>(), cv.data_ptr<float>(),
+                       starts.data_ptr<int>(), cv.data_ptr<float>(), nullptr,
                        attn.data_ptr<float>(), B, C, EP, (int)E,
                        cur_stream());
+}
+
+// attention_fwd that also emits cv rounded to bf16 (cvb [B, EP])
+void attention_fwd_cvb(torch::Tensor ccv, torch::Tensor a,
+                       torch::Tensor starts, torch::Tensor cv,
+                       torch::Tensor cvb, torch::Tensor attn, int64_t E) {
+  CHK_CUDA(ccv); CHK_CONTIG(ccv); CHK_DT(ccv, torch::kBFloat16);
+  CHK_DT(a, torch::kFloat32); CHK_DT(cv, torch::kFloat32);
+  CHK_DT(attn, torch::kFloat32); CHK_DT(starts, torch::kInt32);
+  CHK_DT(cvb, torch::kBFloat16); CHK_CONTIG(cvb); CHK_CONTIG(cv);
+  CHK_CONTIG(attn); CHK_CONTIG(starts);
+  const int B = ccv.size(0), C = ccv.size(1), EP = ccv.size(2);
+  TORCH_CHECK(cv.numel() == (long)B * EP && cvb.numel() == (long)B * EP &&
+              attn.numel() == (long)B * C && starts.numel() == (long)B * C &&
+              a.numel() == EP, "attention_fwd_cvb shapes");
+  launch_attention_fwd(ccv.data_ptr(), a.data_ptr<float>(),
+                       starts.data_ptr<int>(), cv.data_ptr<float>(),
+                       cvb.data_ptr(), attn.data_ptr<float>(), B, C, EP,
+                       (int)E, cur_stream());
+}
+
+// compact attention backward: writes ds [B*C] f32 and the da partials, no
+// dccv.  dcv is f32 or bf16 [B, EP].
+void attention_bwd_compact(torch::Tensor dcv, torch::Tensor dattn,
+                           torch::Tensor ccv, torch::Tensor a,
+                           torch::Tensor starts, torch::Tensor attn,
+                           torch::Tensor ds, torch::Tensor da, int64_t E,
+                           bool has_dattn) {
+  CHK_CUDA(dcv); CHK_CONTIG(dcv); CHK_CONTIG(ccv);
+  CHK_DT(ccv, torch::kBFloat16);
+  const bool dcv_bf16 = dcv.scalar_type() == torch::kBFloat16;
+  TORCH_CHECK(dcv_bf16 || dcv.scalar_type() == torch::kFloat32,
+              "dcv must be f32 or bf16");
+  CHK_DT(ds, torch::kFloat32); CHK_CONTIG(ds);
+  CHK_DT(da, torch::kFloat32); CHK_CONTIG(da);
+  CHK_DT(attn, torch::kFloat32); CHK_CONTIG(attn);
+  CHK_DT(a, torch::kFloat32); CHK_DT(starts, torch::kInt32);
+  CHK_CONTIG(starts);
+  const int B = ccv.size(0), C = ccv.size(1), EP = ccv.size(2);
+  TORCH_CHECK(dcv.numel() == (long)B * EP && ds.numel() == (long)B * C &&
+              da.numel() == (long)B * EP && attn.numel() == (long)B * C &&
+              starts.numel() == (long)B * C && a.numel() == EP && EP <= 384,
+              "attention_bwd_compact shapes");
+  if (has_dattn) {
+    CHK_DT(dattn, torch::kFloat32); CHK_CONTIG(dattn);
+    TORCH_CHECK(dattn.numel() == (long)B * C, "dattn shape");
+  }
+  launch_attention_bwd(dcv.data_ptr(), dcv_bf16 ? 1 : 0,
+                       has_dattn ? dattn.data_ptr<float>() : nullptr,
+                       ccv.data_ptr(), a.data_ptr<float>(),
+                       starts.data_ptr<int>(), attn.data_ptr<float>(),
+                       nullptr, ds.data_ptr<float>(), da.data_ptr<float>(),
+                       B, C, EP, (int)E, has_dattn ? 1 : 0, cur_stream());
+}
+
+// combiner backward that rebuilds dout = bf16(attn*dcv + ds*a) in
+// registers (EP = 128); attn/ds [M] f32, dcv [M / C, 128] f32 or bf16
+void combiner_bwd_recompute(torch::Tensor attn, torch::Tensor ds,
+                            torch::Tensor dcv, torch::Tensor a, int64_t C,
+                            torch::Tensor z, torch::Tensor out,
+                            torch::Tensor mean, torch::Tensor rstd,
+                            torch::Tensor gamma, torch::Tensor beta,
+                            torch::Tensor dz, torch::Tensor dgamma,
+                            torch::Tensor dbeta, int64_t E, double p) {
+  CHK_CUDA(z); CHK_CONTIG(z); CHK_DT(z, torch::kBFloat16);
+  CHK_CONTIG(out); CHK_DT(out, torch::kBFloat16);
+  CHK_CONTIG(dz); CHK_DT(dz, torch::kBFloat16);
+  CHK_CONTIG(attn); CHK_DT(attn, torch::kFloat32);
+  CHK_CONTIG(ds); CHK_DT(ds, torch::kFloat32);
+  CHK_CONTIG(dcv); CHK_CONTIG(a); CHK_DT(a, torch::kFloat32);
+  CHK_DT(mean, torch::kFloat32); CHK_DT(rstd, torch::kFloat32);
+  CHK_DT(gamma, torch::kFloat32); CHK_DT(dgamma, torch::kFloat32);
+  CHK_DT(dbeta, torch::kFloat32);
+  const bool dcv_bf16 = dcv.scalar_type() == torch::kBFloat16;
+  TORCH_CHECK(dcv_bf16 || dcv.scalar_type() == torch::kFloat32,
+              "dcv must be f32 or bf16");
+  const long M = z.size(0);
+  const int EP = z.size(1);
+  TORCH_CHECK(EP == 128 && C > 0 && M % C == 0 && M < (1L << 31) &&
+              attn.numel() == M && ds.numel() == M &&
+              dcv.numel() == (M / C) * EP && a.numel() == EP &&
+              out.numel() == M * EP && dz.numel() == M * EP &&
+              mean.numel() == M && rstd.numel() == M && gamma.numel() == EP,
+              "combiner_bwd_recompute shapes");
+  const long nblocks = std::min<long>((M + 3) / 4, 1024);
+  TORCH_CHECK(dgamma.numel() == nblocks * EP && dbeta.numel() == nblocks * EP,
+              "dgamma/dbeta partials must be [min(ceil(M/4), 1024), EP]");
+  launch_combiner_bwd_recompute(
+      attn.data_ptr<float>(), ds.data_ptr<float>(), dcv.data_ptr(),
+      dcv_bf16 ? 1 : 0, a.data_ptr<float>(), (int)C, z.data_ptr(),
+      out.data_ptr(), mean.data_ptr<float>(), rstd.data_ptr<float>(),
+      gamma.data_ptr<float>(), beta.data_ptr<float>(), dz.data_ptr(),
+      dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), M, (int)E, (float)p,
+      cur_stream());
 }
 
 void attention_bwd(torch::Tensor dcv, torch::Tensor dattn, torch::Tensor ccv,
@@ -315,12 +419,13 @@ void attention_bwd(torch::Tensor dcv, torch::Tensor dattn, torch::Tensor ccv,
   CHK_CUDA(dcv); CHK_CONTIG(dcv); CHK_DT(dcv, torch::kFloat32);
   CHK_DT(dccv, torch::kBFloat16); CHK_DT(da, torch::kFloat32);
   const int B = ccv.size(0), C = ccv.size(1), EP = ccv.size(2);
-  launch_attention_bwd(dcv.data_ptr<float>(),
+  TORCH_CHECK(dccv.data_ptr() != nullptr, "dccv must be allocated");
+  launch_attention_bwd(dcv.data_ptr<float>(), 0,
                        has_dattn ? dattn.data_ptr<float>() : nullptr,
                        ccv.data_ptr(), a.data_ptr<float>(),
                        starts.data_ptr<int>(), attn.data_ptr<float>(),
-                       dccv.data_ptr(), da.data_ptr<float>(), B, C, EP,
-                       (int)E, has_dattn ? 1 : 0, cur_stream());
+                       dccv.data_ptr(), nullptr, da.data_ptr<float>(), B, C,
+                       EP, (int)E, has_dattn ? 1 : 0, cur_stream());
 }
 
 void logsoftmax_nll_fwd(torch::Tensor logits, torch::Tensor label,
@@ -766,9 +871,51 @@ void slab_sum_bf16(torch::Tensor partials, torch::Tensor out) {
   CHK_CONTIG(out); CHK_DT(out, torch::kBFloat16);
   const long N = out.numel();
   const long S = partials.numel() / N;
-  TORCH_CHECK(S * N == partials.numel() && N % 4 == 0, "slab shapes");
+  TORCH_CHECK(N > 0 && S * N == partials.numel(), "slab shapes");
   launch_slab_sum_bf16(partials.data_ptr<float>(), out.data_ptr(), (int)S,
                        N, cur_stream());
+}
+
+// dgamma + dbeta partial slabs in one launch (same tree as slab_sum_f32)
+void slab_sum2_f32(torch::Tensor p0, torch::Tensor p1, torch::Tensor out0,
+                   torch::Tensor out1) {
+  CHK_CUDA(p0); CHK_CONTIG(p0); CHK_DT(p0, torch::kFloat32);
+  CHK_CUDA(p1); CHK_CONTIG(p1); CHK_DT(p1, torch::kFloat32);
+  CHK_CONTIG(out0); CHK_DT(out0, torch::kFloat32);
+  CHK_CONTIG(out1); CHK_DT(out1, torch::kFloat32);
+  const int N = (int)out0.numel();
+  TORCH_CHECK(N > 0 && out1.numel() == N && p0.numel() == p1.numel() &&
+              p0.numel() % N == 0, "slab_sum2_f32 shapes");
+  launch_slab_sum2_f32(p0.data_ptr<float>(), p1.data_ptr<float>(),
+                       out0.data_ptr<float>(), out1.data_ptr<float>(),
+                       (int)(p0.numel() / N), N, cur_stream());
+}
+
+// acc_p [S, 2] -> acc [2], loss [1] = acc[0] / acc[1]
+void loss_reduce(torch::Tensor acc_p, torch::Tensor acc, torch::Tensor loss) {
+  CHK_CUDA(acc_p); CHK_CONTIG(acc_p); CHK_DT(acc_p, torch::kFloat32);
+  CHK_CONTIG(acc); CHK_DT(acc, torch::kFloat32);
+  CHK_CONTIG(loss); CHK_DT(loss, torch::kFloat32);
+  TORCH_CHECK(acc.numel() == 2 && loss.numel() == 1 &&
+              acc_p.numel() % 2 == 0, "loss_reduce shapes");
+  launch_loss_reduce(acc_p.data_ptr<float>(), acc.data_ptr<float>(),
+                     loss.data_ptr<float>(), (int)(acc_p.numel() / 2),
+                     cur_stream());
+}
+
+// wgrad partial slabs [S, KP, EP] f32 -> dw [EP, KP] bf16
+void wgrad_reduce(torch::Tensor partials, torch::Tensor dw) {
+  CHK_CUDA(partials); CHK_CONTIG(partials);
+  CHK_DT(partials, torch::kFloat32);
+  CHK_CUDA(dw); CHK_CONTIG(dw); CHK_DT(dw, torch::kBFloat16);
+  TORCH_CHECK(partials.dim() == 3 && dw.dim() == 2, "wgrad_reduce dims");
+  const long S = partials.size(0), KP = partials.size(1),
+             EP = partials.size(2);
+  TORCH_CHECK(S > 0 && S < (1 << 20) && KP % 4 == 0 && EP % 32 == 0 &&
+              KP > 0 && EP > 0 && dw.size(0) == EP && dw.size(1) == KP,
+              "wgrad_reduce shapes");
+  launch_wgrad_reduce(partials.data_ptr<float>(), dw.data_ptr(), (int)S,
+                      (int)KP, (int)EP, cur_stream());
 }
 
 void slab_sum_f32(torch::Tensor p, torch::Tensor out) {
@@ -971,6 +1118,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("combiner_bwd", &combiner_bwd);
   m.def("attention_fwd", &attention_fwd);
   m.def("attention_bwd", &attention_bwd);
+  m.def("attention_fwd_cvb", &attention_fwd_cvb);
+  m.def("attention_bwd_compact", &attention_bwd_compact);
+  m.def("combiner_bwd_recompute", &combiner_bwd_recompute);
+  m.def("slab_sum2_f32", &slab_sum2_f32);
+  m.def("loss_reduce", &loss_reduce);
+  m.def("wgrad_reduce", &wgrad_reduce);
   m.def("logsoftmax_nll_fwd", &logsoftmax_nll_fwd);
   m.def("logsoftmax_nll_bwd", &logsoftmax_nll_bwd);
   m.def("wgrad", &wgrad);

@@ -400,13 +400,24 @@ __device__ __forceinline__ float half_wave_reduce_sum(float x) {
   return x;
 }
 
+//
+// MODE 0 reads dout from memory.  MODE 1/2 are the dout-RECOMPUTING form
+// behind the compact attention backward: dout is the attention pool's
+// dccv, which is never written; each half-wave loads attn[row], ds[row]
+// and its four dcv[row / C] columns (MODE 1: fp32, MODE 2: bf16 — all
+// L2-resident) and rebuilds bf16(attn*dcv + ds*a) in registers through
+// dccv_elem().  Grid, row-to-wave mapping and the dgamma/dbeta partial
+// layout are shared by all modes, so those sums keep their order.
+template <int MODE>
 __global__ __launch_bounds__(256) void combiner_bwd_v2_kernel(
     const bf16* __restrict__ dout, const bf16* __restrict__ z,
     const bf16* __restrict__ out, const float* __restrict__ mean,
     const float* __restrict__ rstd, const float* __restrict__ gamma,
     const float* __restrict__ beta, bf16* __restrict__ dz,
     float* __restrict__ dgamma_part, float* __restrict__ dbeta_part, long M,
-    int E, float p, float inv1mp) {
+    int E, float p, float inv1mp, const float* __restrict__ attn,
+    const float* __restrict__ ds, const void* __restrict__ dcv,
+    const float* __restrict__ att_a, unsigned C) {
   const int EP = 128;
   const int lane = threadIdx.x & (WAVE - 1);
   const int wave = threadIdx.x / WAVE;
@@ -418,12 +429,33 @@ __global__ __launch_bounds__(256) void combiner_bwd_v2_kernel(
   float g_c[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) g_c[j] = gamma[c0 + j];
+  // the attention vector sits in LDS, not in four registers per lane:
+  // with it the recomputing modes need 71 VGPRs (7 waves/SIMD), without
+  // 78 (6); a 64-VGPR cap through __launch_bounds__ spills
+  __shared__ f32x4 lds_att[32];
+  if (MODE != 0) {
+    if (threadIdx.x < 32)
+      lds_att[threadIdx.x] = *(const f32x4*)(att_a + threadIdx.x * 4);
+    __syncthreads();
+  }
   float acc_dg[4] = {}, acc_db[4] = {};
 
   const long wpb = blockDim.x / WAVE;           // wave-pairs per block
   long pr = (long)blockIdx.x * wpb + wave;      // row-pair index
   const long pstride = (long)gridDim.x * wpb;
   const long npairs = (M + 1) >> 1;
+  // recomputing modes: method index b = row / C kept incrementally (one
+  // divide per thread, then a step of 2*pstride rows per iteration);
+  // M < 2^31 is checked by the caller
+  unsigned mb = 0, mrem = 0, mb_step = 0, mrem_step = 0;
+  if (MODE != 0) {
+    const unsigned row0 = (unsigned)(2 * pr + half);
+    mb = row0 / C;
+    mrem = row0 - mb * C;
+    const unsigned rstep = (unsigned)(2 * pstride);
+    mb_step = rstep / C;
+    mrem_step = rstep - mb_step * C;
+  }
   for (; pr < npairs; pr += pstride) {
     const long row = 2 * pr + half;
     const bool rok = row < M;
@@ -432,8 +464,27 @@ __global__ __launch_bounds__(256) void combiner_bwd_v2_kernel(
     bf16x4 zv = {}, dy4 = {}, ov4 = {};
     if (rok) {
       zv = *(const bf16x4*)(z + row * EP + c0);
-      dy4 = *(const bf16x4*)(dout + row * EP + c0);
       ov4 = *(const bf16x4*)(out + row * EP + c0);
+      if (MODE == 0) {
+        dy4 = *(const bf16x4*)(dout + row * EP + c0);
+      } else {
+        const unsigned b = mb;
+        const float at = attn[row];
+        const float dsc = ds[row];
+        f32x4 dc;
+        if (MODE == 1) {
+          dc = *(const f32x4*)((const float*)dcv + (size_t)b * EP + c0);
+        } else {
+          const bf16x4 d4 =
+              *(const bf16x4*)((const bf16*)dcv + (size_t)b * EP + c0);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) dc[j] = bf2f(d4[j]);
+        }
+        const f32x4 a_c = lds_att[lane & 31];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          dy4[j] = dccv_elem(at, dc[j], dsc, a_c[j]);
+      }
     }
     float xhat[4], du[4];
     float s1 = 0.f, s2 = 0.f;
@@ -463,6 +514,14 @@ __global__ __launch_bounds__(256) void combiner_bwd_v2_kernel(
         o[j] = f2bf(valid ? rs * (h - s1 - xhat[j] * s2) : 0.f);
       }
       *(bf16x4*)(dz + row * EP + c0) = o;
+    }
+    if (MODE != 0) {
+      mb += mb_step;
+      mrem += mrem_step;
+      if (mrem >= C) {
+        mrem -= C;
+        ++mb;
+      }
     }
   }
 
@@ -619,9 +678,10 @@ void launch_combiner_bwd(const void* dout, const void* z, const void* out,
   if (EP == 128 && (v2e == nullptr || v2e[0] != '0')) {
     // SAME grid as v1: the host sums dgamma/dbeta partials over this many
     // block rows, so every block must write its row (idle pairs write 0)
-    combiner_bwd_v2_kernel<<<grid, block, 0, stream>>>(
+    combiner_bwd_v2_kernel<0><<<grid, block, 0, stream>>>(
         (const bf16*)dout, (const bf16*)z, (const bf16*)out, mean, rstd,
-        gamma, beta, (bf16*)dz, dgamma, dbeta, M, E, p, inv1mp);
+        gamma, beta, (bf16*)dz, dgamma, dbeta, M, E, p, inv1mp, nullptr,
+        nullptr, nullptr, nullptr, 1u);
     return;
   }
 #define BCASE(np)                                                             \
@@ -636,6 +696,33 @@ void launch_combiner_bwd(const void* dout, const void* z, const void* out,
       printf("combiner_bwd: unsupported EP=%d\n", EP);
   }
 #undef BCASE
+}
+
+// dout-recomputing combiner backward (EP = 128 only): dout[row, e] =
+// bf16(attn[row]*dcv[row / C, e] + ds[row]*a[e]) is rebuilt in registers.
+// Same grid as launch_combiner_bwd, so the dgamma/dbeta partials match.
+void launch_combiner_bwd_recompute(const float* attn, const float* ds,
+                                   const void* dcv, int dcv_bf16,
+                                   const float* att_a, int C, const void* z,
+                                   const void* out, const float* mean,
+                                   const float* rstd, const float* gamma,
+                                   const float* beta, void* dz, float* dgamma,
+                                   float* dbeta, long M, int E, float p,
+                                   hipStream_t stream) {
+  const int block = 256;
+  const int wpb = block / WAVE;
+  const int grid = (int)min((M + wpb - 1) / wpb, (long)COMBINER_BWD_MAX_GRID);
+  const float inv1mp = p > 0.f ? 1.0f / (1.0f - p) : 1.0f;
+  if (dcv_bf16)
+    combiner_bwd_v2_kernel<2><<<grid, block, 0, stream>>>(
+        nullptr, (const bf16*)z, (const bf16*)out, mean, rstd, gamma, beta,
+        (bf16*)dz, dgamma, dbeta, M, E, p, inv1mp, attn, ds, dcv, att_a,
+        (unsigned)C);
+  else
+    combiner_bwd_v2_kernel<1><<<grid, block, 0, stream>>>(
+        nullptr, (const bf16*)z, (const bf16*)out, mean, rstd, gamma, beta,
+        (bf16*)dz, dgamma, dbeta, M, E, p, inv1mp, attn, ds, dcv, att_a,
+        (unsigned)C);
 }
 
 }  // extern "C"

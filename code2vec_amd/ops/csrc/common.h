@@ -17,6 +17,20 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 __device__ __forceinline__ float bf2f(bf16 x) { return (float)x; }
 __device__ __forceinline__ bf16 f2bf(float x) { return (bf16)x; }
 
+// One element of the attention backward's gradient w.r.t. the combiner
+// output: bf16(attn*dcv + ds*a).  Written out with contraction off — the
+// ds*a product is rounded, then one FMA adds attn*dcv — which is what the
+// dense attention_bwd_kernel has always compiled to.  attention_bwd (dense
+// form) and the dout-recomputing combiner backward both call it, so the
+// tensor the former writes and the registers the latter rebuilds hold the
+// same bits whatever the surrounding code or compiler version.
+__device__ __forceinline__ bf16 dccv_elem(float at, float dcv, float dsc,
+                                          float a) {
+#pragma clang fp contract(off)
+  const float t = dsc * a;
+  return f2bf(__builtin_fmaf(at, dcv, t));
+}
+
 // ---------------------------------------------------------------------------
 // Counter-based RNG for dropout masks: deterministic, stateless, cheap
 // (32-bit finalizer; the backward never replays it — the mask is recovered

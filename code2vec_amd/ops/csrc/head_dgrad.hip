@@ -141,6 +141,43 @@ __global__ __launch_bounds__(256) void slab_sum_bf16_kernel(
   if (i2 < N) out[i2] = f2bf(acc2);
 }
 
+// Same two chains, same ascending slab order per chain, but 8 slab loads
+// per chain are issued before the first add (16 in flight per thread
+// instead of 2): the 71-deep dependent load chain at top11 becomes 9
+// batches.  Each accumulator sees the same addends in the same order, so
+// the result has the same bits as slab_sum_bf16_kernel.
+__global__ __launch_bounds__(256) void slab_sum_bf16_u8_kernel(
+    const float* __restrict__ partials, bf16* __restrict__ out, int S,
+    long N) {
+  const long half = (N + 1) / 2;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= half) return;
+  const long i2 = i + half;
+  const bool ok2 = i2 < N;
+  float acc = 0.f, acc2 = 0.f;
+  for (int s = 0; s < S; s += 8) {
+    float v[8], v2[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      if (s + k < S) {
+        v[k] = __builtin_nontemporal_load(partials + (long)(s + k) * N + i);
+        if (ok2)
+          v2[k] =
+              __builtin_nontemporal_load(partials + (long)(s + k) * N + i2);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      if (s + k < S) {
+        acc += v[k];
+        if (ok2) acc2 += v2[k];
+      }
+    }
+  }
+  out[i] = f2bf(acc);
+  if (ok2) out[i2] = f2bf(acc2);
+}
+
 extern "C" {
 
 void launch_transpose_w(const void* w, void* wt, long L,
@@ -152,8 +189,14 @@ void launch_transpose_w(const void* w, void* wt, long L,
 void launch_slab_sum_bf16(const float* partials, void* out, int S, long N,
                           hipStream_t stream) {
   const long half = (N + 1) / 2;
-  slab_sum_bf16_kernel<<<(half + 255) / 256, 256, 0, stream>>>(
-      partials, (bf16*)out, S, N);
+  // C2V_SLAB_U8=0 reverts to the two-loads-in-flight kernel
+  static const char* u8e = getenv("C2V_SLAB_U8");
+  if (u8e == nullptr || u8e[0] != '0')
+    slab_sum_bf16_u8_kernel<<<(half + 255) / 256, 256, 0, stream>>>(
+        partials, (bf16*)out, S, N);
+  else
+    slab_sum_bf16_kernel<<<(half + 255) / 256, 256, 0, stream>>>(
+        partials, (bf16*)out, S, N);
 }
 
 void launch_head_dgrad(const void* dlogits, const void* wt, float* partials,

@@ -8,8 +8,7 @@ combiner forward (fused LN/tanh/dropout epilogue), combiner dgrad
 ~3.5x off), the head forward (+online-softmax stats epilogue) and the
 fused recompute-G head backward (dW/dbias/dcv).  rocBLAS/hipBLASLt
 remain only where they measured faster or equal: the head forward above
-the vocab gate with C2V_HF_AIMG=0, and small reductions torch already
-does at bandwidth (the wgrad partial-slab sum).
+the vocab gate with C2V_HF_AIMG=0.
 
 Numerical contracts are defined by ops/reference.py; tests compare against
 it in fp32.
@@ -62,6 +61,18 @@ _DGRAD2 = os.environ.get("C2V_DGRAD2", "1") == "1"
 # C2V_FUSED_HEAD=0 falls back to the unfused OutputHead+FusedLogSoftmaxNLL
 # chain (kept for A/B and as the general-shape path).
 FUSED_HEAD = os.environ.get("C2V_FUSED_HEAD", "1") == "1"
+# combiner + attention pool as ONE autograd node whose backward never
+# writes the attention gradient dccv (compact attention_bwd + recomputing
+# combiner_bwd) and whose forward also emits cv in bf16.  C2V_FUSED_CAP=0
+# reverts to the CombinerLNTanh -> AttentionPool -> .to(bf16) chain.
+FUSED_CAP = os.environ.get("C2V_FUSED_CAP", "1") == "1"
+# one-launch reductions; each =0 reverts to the chain it replaced
+_WGRAD_REDUCE = os.environ.get("C2V_WGRAD_REDUCE", "1") == "1"  # sum+t+cast
+_SLAB_SUM2 = os.environ.get("C2V_SLAB_SUM2", "1") == "1"  # dgamma+dbeta
+# loss partials -> acc and acc[0]/acc[1] in one launch.  Same bits, one
+# launch fewer, but its step-time gain could not be told from the
+# run-to-run spread (PERF.md, "Backward fusions"), so it is opt-in.
+_LOSS_REDUCE = os.environ.get("C2V_LOSS_REDUCE", "0") == "1"
 _NONE_T = torch.Tensor()  # "not provided" sentinel for optional kernel args
 
 # Owner-buffer gradient flow for the embedding tables (parallel/ddp.py):
@@ -351,6 +362,33 @@ def _slab_sum(p: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _slab_sum_pair(p0: torch.Tensor, p1: torch.Tensor):
+    """Two equal-shape partial slabs [S, N] -> two [N] f32 sums in ONE
+    launch (the dgamma/dbeta pair); same per-column tree, same bits as
+    two _slab_sum calls."""
+    if not _SLAB_SUM2:
+        return _slab_sum(p0), _slab_sum(p1)
+    out0 = torch.empty(p0.shape[-1], dtype=torch.float32, device=p0.device)
+    out1 = torch.empty_like(out0)
+    ext().slab_sum2_f32(p0, p1, out0, out1)
+    return out0, out1
+
+
+def _wgrad_reduce(partials: torch.Tensor) -> torch.Tensor:
+    """Split-K wgrad slabs [S, KP, EP] f32 -> dw [EP, KP] bf16.  One
+    kernel sums, transposes and casts (fixed summation order, see
+    wgrad_reduce_kernel); C2V_WGRAD_REDUCE=0 is the torch
+    sum -> .t().contiguous() -> .to(bf16) chain it replaced, whose reduce
+    order differs in the last bits."""
+    S, KP, EP = partials.shape
+    if not (_WGRAD_REDUCE and partials.is_cuda and KP % 4 == 0
+            and EP % 32 == 0):
+        return partials.sum(dim=0).t().contiguous().to(torch.bfloat16)
+    dw = torch.empty(EP, KP, dtype=torch.bfloat16, device=partials.device)
+    ext().wgrad_reduce(partials, dw)
+    return dw
+
+
 def _group_by_index(idx: torch.Tensor, table_rows: int,
                     pool_tag: Optional[str] = None,
                     with_cursor: bool = False):
@@ -408,6 +446,36 @@ def _group_by_index(idx: torch.Tensor, table_rows: int,
     return sorted_idx, perm, counts
 
 
+def _combiner_dx_dw(x, w, dz):
+    """dx and dw of the combiner GEMM from dz (shared by CombinerLNTanh and
+    CombinerAttentionPool backward)."""
+    M, EP = dz.shape
+    # dgrad: plain GEMM -> rocBLAS (TunableOp-tuned).  A hand-written
+    # direct-fragment kernel (ops/csrc/dgrad.hip) measured 192 us vs
+    # rocBLAS's 64 us at the top11 shape (8-wave full-KP duplicates B
+    # L2 traffic) and is kept only as a reference; re-enable via
+    # C2V_CUSTOM_DGRAD=1 for experiments.
+    if os.environ.get("C2V_CUSTOM_DGRAD") == "1":
+        w2 = w.t().contiguous()
+        dx = torch.empty(M, w.shape[1], dtype=torch.bfloat16,
+                         device=w.device)
+        ext().dgrad(dz, w2, dx)
+    else:
+        dx = _combiner_dgrad(dz, w)
+    # wgrad: custom split-K MFMA kernel for the skinny big-K shape
+    # (hipBLASLt is ~3.5x off there); partial slabs summed here.
+    KP = x.shape[1]
+    if EP <= 128 and KP <= 512:
+        nsplit = 256
+        partials = torch.empty(nsplit, KP, EP, dtype=torch.float32,
+                               device=x.device)
+        ext().wgrad(x, dz, partials)
+        dw = _wgrad_reduce(partials)
+    else:
+        dw = (x.t() @ dz).t().contiguous()
+    return dx, dw
+
+
 class CombinerLNTanh(torch.autograd.Function):
     """K3-K6: MFMA GEMM (x @ w) -> LayerNorm(E) -> tanh -> dropout, fused.
 
@@ -449,31 +517,8 @@ class CombinerLNTanh(torch.autograd.Function):
             dout.contiguous(), z, out, mean, rstd, gamma, beta, dz, dgamma_p,
             dbeta_p, E, p,
         )
-        dgamma = _slab_sum(dgamma_p)
-        dbeta = _slab_sum(dbeta_p)
-        # dgrad: plain GEMM -> rocBLAS (TunableOp-tuned).  A hand-written
-        # direct-fragment kernel (ops/csrc/dgrad.hip) measured 192 us vs
-        # rocBLAS's 64 us at the top11 shape (8-wave full-KP duplicates B
-        # L2 traffic) and is kept only as a reference; re-enable via
-        # C2V_CUSTOM_DGRAD=1 for experiments.
-        if os.environ.get("C2V_CUSTOM_DGRAD") == "1":
-            w2 = w.t().contiguous()
-            dx = torch.empty(M, w.shape[1], dtype=torch.bfloat16,
-                             device=w.device)
-            ext().dgrad(dz, w2, dx)
-        else:
-            dx = _combiner_dgrad(dz, w)
-        # wgrad: custom split-K MFMA kernel for the skinny big-K shape
-        # (hipBLASLt is ~3.5x off there); partial slabs summed here.
-        KP = x.shape[1]
-        if EP <= 128 and KP <= 512:
-            nsplit = 256
-            partials = torch.empty(nsplit, KP, EP, dtype=torch.float32,
-                                   device=x.device)
-            ext().wgrad(x, dz, partials)
-            dw = partials.sum(dim=0).t().contiguous().to(torch.bfloat16)
-        else:
-            dw = (x.t() @ dz).t().contiguous()
+        dgamma, dbeta = _slab_sum_pair(dgamma_p, dbeta_p)
+        dx, dw = _combiner_dx_dw(x, w, dz)
         return dx, dw, dgamma, dbeta, None, None, None
 
 
@@ -519,15 +564,14 @@ class FusedGatherCombiner(torch.autograd.Function):
         dbeta_p = torch.empty(nblocks, EP, dtype=torch.float32, device=z.device)
         ext().combiner_bwd(dout.contiguous(), z, out, mean, rstd, gamma,
                            beta, dz, dgamma_p, dbeta_p, E, p)
-        dgamma = _slab_sum(dgamma_p)
-        dbeta = _slab_sum(dbeta_p)
+        dgamma, dbeta = _slab_sum_pair(dgamma_p, dbeta_p)
         # dW: re-gathering split-K wgrad (X is never materialized)
         if EP <= 128 and KP <= 512:
             partials = torch.empty(256, KP, EP, dtype=torch.float32,
                                    device=z.device)
             ext().wgrad_gather(starts, paths, ends, term_w, path_w, dz,
                                partials, KP)
-            dw = partials.sum(dim=0).t().contiguous().to(torch.bfloat16)
+            dw = _wgrad_reduce(partials)
         else:
             x = GatherConcat.apply(starts, paths, ends, term_w, path_w)
             dw = (x.t() @ dz).t().contiguous()
@@ -576,6 +620,93 @@ class AttentionPool(torch.autograd.Function):
             ccv, a, starts, attn, dccv, da_p, ctx.E, has_dattn,
         )
         return dccv, _slab_sum(da_p), None, None
+
+
+class CombinerAttentionPool(torch.autograd.Function):
+    """K3-K9 as one autograd node (EP = 128): combiner_fwd, then
+    attention_fwd, returning cv (f32), attn and cv rounded to bf16 (what
+    the output head consumes; the kernel emits it, so no cast kernel runs).
+
+    Backward never materializes dccv [B*C, EP], the attention pool's
+    gradient w.r.t. the combiner output: the compact attention_bwd writes
+    only ds [B*C] (plus the da partials) and the recomputing combiner_bwd
+    rebuilds each element bf16(attn*dcv + ds*a) in registers, through the
+    same device function the dense kernel uses, so every result has the
+    bits of the CombinerLNTanh -> AttentionPool -> .to(bf16) chain.  The
+    bf16 gradient of the bf16 cv output is read by the kernels directly;
+    a gradient on the f32 cv output, if there is one as well, is added
+    first."""
+
+    @staticmethod
+    def forward(ctx, x, w, gamma, beta, a, starts, E: int, p: float,
+                training: bool):
+        B, C = starts.shape
+        M = x.shape[0]
+        EP = w.shape[0]
+        assert EP == 128 and M == B * C
+        starts = starts.contiguous()
+        dev = x.device
+        out = torch.empty(M, EP, dtype=torch.bfloat16, device=dev)
+        z = torch.empty(M, EP, dtype=torch.bfloat16, device=dev)
+        mean = torch.empty(M, dtype=torch.float32, device=dev)
+        rstd = torch.empty(M, dtype=torch.float32, device=dev)
+        p_eff = float(p) if training else 0.0
+        seed, off_t = (_philox_state(dev) if p_eff > 0.0
+                       else (0, _philox_state(dev)[1]))
+        ext().combiner_fwd(x, w, gamma, beta, out, z, mean, rstd, E, p_eff,
+                           seed, off_t, _FWD_EPI)
+        cv = torch.empty(B, EP, dtype=torch.float32, device=dev)
+        cvb = torch.empty(B, EP, dtype=torch.bfloat16, device=dev)
+        attn = torch.empty(B, C, dtype=torch.float32, device=dev)
+        ext().attention_fwd_cvb(out.view(B, C, EP), a, starts, cv, cvb, attn,
+                                E)
+        ctx.save_for_backward(x, w, gamma, beta, a, starts, z, mean, rstd,
+                              out, attn)
+        ctx.meta = (E, p_eff)
+        ctx.set_materialize_grads(False)
+        return cv, attn, cvb
+
+    @staticmethod
+    def backward(ctx, dcv32, dattn, dcvb):
+        (x, w, gamma, beta, a, starts, z, mean, rstd, out,
+         attn) = ctx.saved_tensors
+        E, p = ctx.meta
+        B, C = starts.shape
+        M, EP = z.shape
+        dev = z.device
+        if dcv32 is not None and dcvb is not None:
+            dcv = dcv32 + dcvb  # f32 sum, as autograd's accumulation did
+        elif dcvb is not None:
+            dcv = dcvb          # bf16, read by the kernels as is
+        elif dcv32 is not None:
+            dcv = dcv32
+        else:
+            dcv = torch.zeros(B, EP, dtype=torch.float32, device=dev)
+        dcv = dcv.contiguous()
+        ds = torch.empty(M, dtype=torch.float32, device=dev)
+        da_p = torch.empty(B, EP, dtype=torch.float32, device=dev)
+        has_dattn = dattn is not None
+        dattn = dattn.contiguous() if has_dattn else _NONE_T
+        ext().attention_bwd_compact(dcv, dattn, out.view(B, C, EP), a,
+                                    starts, attn, ds, da_p, E, has_dattn)
+        da = _slab_sum(da_p)
+        dz = torch.empty(M, EP, dtype=torch.bfloat16, device=dev)
+        nblocks = min((M + 4 - 1) // 4, 1024)
+        dgamma_p = torch.empty(nblocks, EP, dtype=torch.float32, device=dev)
+        dbeta_p = torch.empty(nblocks, EP, dtype=torch.float32, device=dev)
+        ext().combiner_bwd_recompute(attn.view(-1), ds, dcv, a, C, z, out,
+                                     mean, rstd, gamma, beta, dz, dgamma_p,
+                                     dbeta_p, E, p)
+        dgamma, dbeta = _slab_sum_pair(dgamma_p, dbeta_p)
+        dx, dw = _combiner_dx_dw(x, w, dz)
+        return dx, dw, dgamma, dbeta, da, None, None, None, None
+
+
+def combiner_attention_pool_supported(x, w) -> bool:
+    """Gates for CombinerAttentionPool: device tensors, EP = 128, grad
+    mode on (eval/export/predict keep the separate Functions)."""
+    return (FUSED_CAP and x.is_cuda and w.shape[0] == 128
+            and torch.is_grad_enabled() and x.shape[0] < (1 << 31))
 
 
 class OutputHead(torch.autograd.Function):
@@ -650,12 +781,20 @@ class OutputHead(torch.autograd.Function):
 
 def _acc_reduce(acc_part):
     """Deterministic (fixed-order) reduction of per-block loss partials
-    [S, 2] -> acc[2] = (sum w_y*nll, sum w_y).  The previous atomic-add
-    accumulation was ordering-nondeterministic at the fp32 ulp level and
-    made identical runs diverge after two steps of bf16 rounding."""
+    [S, 2] -> (acc[2] = (sum w_y*nll, sum w_y), loss = acc[0] / acc[1]).
+    The previous atomic-add accumulation was ordering-nondeterministic at
+    the fp32 ulp level and made identical runs diverge after two steps of
+    bf16 rounding.  One kernel writes acc and the quotient (same column
+    tree as slab_sum_f32, correctly rounded division) with
+    C2V_LOSS_REDUCE=1; the default is slab_sum_f32 + the torch
+    select/divide."""
     acc = torch.empty(2, dtype=torch.float32, device=acc_part.device)
+    if _LOSS_REDUCE:
+        loss = torch.empty((), dtype=torch.float32, device=acc_part.device)
+        ext().loss_reduce(acc_part, acc, loss)
+        return acc, loss
     ext().slab_sum_f32(acc_part, acc)
-    return acc
+    return acc, acc[0] / acc[1]
 
 
 def _finalize_stats(logits, pm, ps, label, weight, lse):
@@ -667,7 +806,7 @@ def _finalize_stats(logits, pm, ps, label, weight, lse):
 
 
 def _lsm_stats(logits, label, weight, lse):
-    """Fill lse and return acc from a full pass over logits.  Large L
+    """Fill lse and return (acc, loss) from a full pass over logits.  Large L
     takes the 2-D-grid partials kernel + finalize (the one-block-per-row
     walk is latency-bound at ~3.6 TB/s at L = 261k: 150 -> ~75 us)."""
     B, L = logits.shape
@@ -701,10 +840,9 @@ class FusedLogSoftmaxNLL(torch.autograd.Function):
             # the whole [B, L] matrix
             pm, ps = partials
             del logits._c2v_lsm_partials
-            acc = _finalize_stats(logits, pm, ps, label, weight, lse)
+            acc, loss = _finalize_stats(logits, pm, ps, label, weight, lse)
         else:
-            acc = _lsm_stats(logits, label, weight, lse)
-        loss = acc[0] / acc[1]
+            acc, loss = _lsm_stats(logits, label, weight, lse)
         ctx.save_for_backward(logits, label, weight, lse, acc)
         return loss
 
@@ -863,10 +1001,9 @@ class FusedHeadLoss(torch.autograd.Function):
         if partials is not None:
             pm, ps = partials
             del logits._c2v_lsm_partials
-            acc = _finalize_stats(logits, pm, ps, label, weight, lse)
+            acc, loss = _finalize_stats(logits, pm, ps, label, weight, lse)
         else:
-            acc = _lsm_stats(logits, label, weight, lse)
-        loss = acc[0] / acc[1]
+            acc, loss = _lsm_stats(logits, label, weight, lse)
         ctx.save_for_backward(logits, cv_bf16, w, label, weight, lse, acc)
         # saved_tensors re-wraps the tensor object, so python attributes
         # do not survive — carry the forward's W fragment image on ctx

@@ -4,10 +4,11 @@
 Times each framework op at the top11 flagship shape; variants switch via
 env vars read by ops/functional.py.  Usage (on a GPU box):
     python tools/kbench.py [op ...]
-``row_topk`` (K19 vs torch.topk + torch.logsumexp) and ``table_adam``
-(scatter + cast_clear + adam_bf16 vs the row-gathering table Adam) are not
-in the default set; asked for alone they skip building the model-shaped
-operands.
+``row_topk`` (K19 vs torch.topk + torch.logsumexp), ``table_adam``
+(scatter + cast_clear + adam_bf16 vs the row-gathering table Adam) and
+``bwd_fusions`` (one-launch reductions, compact attention backward and
+recomputing combiner backward vs what they replace) are not in the default
+set; asked for alone they skip building the model-shaped operands.
 """
 
 from __future__ import annotations
@@ -144,6 +145,81 @@ def bench_table_adam(dev, results, rounds=5):
         print(f"# table_adam {tag}: {gbs:.0f} GB/s effective (median, new)")
 
 
+def bench_bwd_fusions(dev, results, rounds=5):
+    """The one-launch reductions against what they replace on the SAME
+    buffers, alternating within each round (median / min), at top11 shapes:
+      wgrad_reduce [256, 320, 128] f32 -> [128, 320] bf16
+        vs torch sum -> .t().contiguous() -> .to(bf16)
+      slab_sum_bf16 [71, 1024*128]: 8 loads in flight per chain vs 1 (the
+        launcher reads C2V_SLAB_U8 once per process: run this case a second
+        time with C2V_SLAB_U8=0 for the old kernel's number)
+      dcv/attn/ds-recomputing combiner_bwd vs the dout-reading one, and
+      compact vs dense attention_bwd."""
+    from code2vec_amd.ops import ext
+
+    g = torch.Generator(device=dev).manual_seed(0)
+    S, KP, EP = 256, 320, 128
+    part = torch.randn(S, KP, EP, generator=g, device=dev)
+    dw = torch.empty(EP, KP, dtype=torch.bfloat16, device=dev)
+    slabs = torch.randn(71, 1024 * 128, generator=g, device=dev)
+    dcv_o = torch.empty(1024, 128, dtype=torch.bfloat16, device=dev)
+
+    B, C, E = 1024, 200, 100
+    M = B * C
+    ccv = torch.tanh(torch.randn(B, C, EP, generator=g, device=dev)).to(
+        torch.bfloat16)
+    ccv[:, :, E:] = 0
+    a = torch.randn(EP, generator=g, device=dev) * 0.2
+    a[E:] = 0
+    starts = torch.randint(1, 1000, (B, C), generator=g, device=dev,
+                           dtype=torch.int32)
+    cv = torch.empty(B, EP, device=dev)
+    attn = torch.empty(B, C, device=dev)
+    ext().attention_fwd(ccv, a, starts, cv, attn, E)
+    dcvb = (torch.randn(B, EP, generator=g, device=dev) * 0.1).to(
+        torch.bfloat16)
+    dcv32 = dcvb.float()
+    dccv = torch.empty_like(ccv)
+    ds = torch.empty(M, device=dev)
+    da_p = torch.empty(B, EP, device=dev)
+    none = torch.empty(0, device=dev)
+    z = torch.randn(M, EP, generator=g, device=dev).to(torch.bfloat16)
+    mean = torch.zeros(M, device=dev)
+    rstd = torch.ones(M, device=dev)
+    gamma = torch.rand(EP, generator=g, device=dev) + 0.5
+    beta = torch.zeros(EP, device=dev)
+    dz = torch.empty(M, EP, dtype=torch.bfloat16, device=dev)
+    dg_p = torch.empty(1024, EP, device=dev)
+    db_p = torch.empty(1024, EP, device=dev)
+    out2 = ccv.view(M, EP)
+
+    cases = {
+        "wgrad_reduce new": lambda: ext().wgrad_reduce(part, dw),
+        "wgrad_reduce torch chain": lambda: part.sum(dim=0).t().contiguous()
+        .to(torch.bfloat16),
+        "slab_sum_bf16 [71,131072]": lambda: ext().slab_sum_bf16(slabs,
+                                                                 dcv_o),
+        "attention_bwd dense": lambda: ext().attention_bwd(
+            dcv32, none, ccv, a, starts, attn, dccv, da_p, E, False),
+        "attention_bwd compact": lambda: ext().attention_bwd_compact(
+            dcvb, none, ccv, a, starts, attn, ds, da_p, E, False),
+        "combiner_bwd dout": lambda: ext().combiner_bwd(
+            dccv.view(M, EP), z, out2, mean, rstd, gamma, beta, dz, dg_p,
+            db_p, E, 0.25),
+        "combiner_bwd recompute": lambda: ext().combiner_bwd_recompute(
+            attn.view(-1), ds, dcvb, a, C, z, out2, mean, rstd, gamma, beta,
+            dz, dg_p, db_p, E, 0.25),
+    }
+    t = {k: [] for k in cases}
+    for _ in range(rounds):
+        for k, fn in cases.items():
+            t[k].append(timeit(fn, iters=20))
+    for k, vals in t.items():
+        vals.sort()
+        results[f"{k} med"] = vals[rounds // 2]
+        results[f"{k} min"] = vals[0]
+
+
 def main():
     if "--help" in sys.argv or "-h" in sys.argv:
         print(__doc__.strip())
@@ -152,11 +228,13 @@ def main():
         print("kbench: needs a GPU (per-kernel timing); run under gpurun")
         return
     dev = torch.device("cuda:0")
-    if sys.argv[1:] in (["row_topk"], ["table_adam"]):
+    if sys.argv[1:] in (["row_topk"], ["table_adam"], ["bwd_fusions"]):
         # needs none of the model-shaped operands built below
         results = {}
         if sys.argv[1] == "row_topk":
             bench_row_topk(dev, results)
+        elif sys.argv[1] == "bwd_fusions":
+            bench_bwd_fusions(dev, results)
         else:
             bench_table_adam(dev, results)
         for k, vv in results.items():
