@@ -204,7 +204,7 @@ class Code2VecHIP(nn.Module):
         else:
             x = Fn.GatherConcat.apply(
                 starts, paths, ends, self.terminal_embedding,
-                self.path_embedding
+                self.path_embedding, self.training
             )
         if y is None and Fn.combiner_attention_pool_supported(
                 x, self.input_weight):

@@ -384,14 +384,16 @@ void launch_adam_bf16(void* p, const void* g, float* master, float* m,
 
 // Table Adam from a deferred gradient record (see adam_table_bf16_kernel);
 // T rows of S columns, S % 4 == 0 and T * S / 4 < 2^32 (checked by the
-// binding).  Also restores the all-zero invariant of counts[0..ncounts).
+// binding).  With clear_counts it also restores the all-zero invariant of
+// counts[0..ncounts); without, the caller clears after every reader of the
+// histogram is done (both tables in one launch, index_group.hip).
 void launch_adam_table_bf16(void* p, const void* gout, const long* perm,
                             int* counts, const int* cursor, float* scratch,
                             float* master, float* m, float* v, long T, int S,
                             long ncounts, long N, long M, int KP, int off0,
                             int off1, int thr, const double* bc_pow, float lr,
                             float b1, float b2, float eps, float wd,
-                            hipStream_t stream) {
+                            int clear_counts, hipStream_t stream) {
   const int block = 256;
   const long n = T * S;
   // same grid rule as launch_adam_bf16
@@ -418,6 +420,7 @@ void launch_adam_table_bf16(void* p, const void* gout, const long* perm,
   else if (D == 4) TADAM_LAUNCH(2, 4);
   else TADAM_LAUNCH(2, 2);
 #undef TADAM_LAUNCH
+  if (!clear_counts) return;
   const int cgrid = (int)min((ncounts + block - 1) / block, (long)4096);
   clear_i32_kernel<<<cgrid > 0 ? cgrid : 1, block, 0, stream>>>(counts,
                                                                 ncounts);

@@ -6,7 +6,10 @@
 #include <torch/extension.h>
 
 #include <ATen/hip/HIPContext.h>
+#include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
+
+#include <map>
 
 #define CHK(x) TORCH_CHECK(x, #x)
 #define CHK_CONTIG(t) TORCH_CHECK((t).is_contiguous(), #t " must be contiguous")
@@ -28,7 +31,17 @@ void launch_embed_scatter_heavy(const int*, const long*, const int*,
 void launch_adam_table_bf16(void*, const void*, const long*, int*, const int*,
                             float*, float*, float*, float*, long, int, long,
                             long, long, int, int, int, int, const double*,
-                            float, float, float, float, float, hipStream_t);
+                            float, float, float, float, float, int,
+                            hipStream_t);
+long group_tables_partials(long, long);
+void launch_group_tables(const int*, const int*, const int*, long, int, int,
+                         int*, int*, int*, int*, int*, int*, long*, int*,
+                         long*, hipStream_t);
+void launch_embed_scatter_heavy_pair(const int*, const long*, const int*,
+                                     float*, int, const int*, const long*,
+                                     const int*, float*, int, const void*,
+                                     long, int, int, hipStream_t);
+void launch_clear_i32_pair(int*, long, int*, long, hipStream_t);
 void launch_count_indices(const int*, int*, long, hipStream_t);
 void launch_cast_clear_rows(float*, const int*, unsigned char*, void*, long,
                             int, hipStream_t);
@@ -1026,13 +1039,13 @@ void embed_scatter_heavy(torch::Tensor sorted_idx, torch::Tensor perm,
 // Row-gathering table Adam: p bf16 [T, S] updated from the deferred record
 // (gout, perm, counts, cursor) instead of a dense gradient; consumes
 // counts (left all-zero) and the heavy rows of `scratch` (re-zeroed).
-void adam_table_bf16(torch::Tensor p, torch::Tensor gout, torch::Tensor perm,
-                     torch::Tensor counts, torch::Tensor cursor,
-                     torch::Tensor scratch, torch::Tensor master,
-                     torch::Tensor m, torch::Tensor v, torch::Tensor bc_pow,
-                     int64_t M, int64_t KP, int64_t off0, int64_t off1,
-                     int64_t thr, double lr, double b1, double b2, double eps,
-                     double wd) {
+static void adam_table_bf16_impl(
+    torch::Tensor p, torch::Tensor gout, torch::Tensor perm,
+    torch::Tensor counts, torch::Tensor cursor, torch::Tensor scratch,
+    torch::Tensor master, torch::Tensor m, torch::Tensor v,
+    torch::Tensor bc_pow, int64_t M, int64_t KP, int64_t off0, int64_t off1,
+    int64_t thr, double lr, double b1, double b2, double eps, double wd,
+    bool clear_counts) {
   CHK_CUDA(p); CHK_CONTIG(p); CHK_DT(p, torch::kBFloat16);
   TORCH_CHECK(p.dim() == 2, "p must be [T, S]");
   const long T = p.size(0);
@@ -1059,7 +1072,173 @@ void adam_table_bf16(torch::Tensor p, torch::Tensor gout, torch::Tensor perm,
       m.data_ptr<float>(), v.data_ptr<float>(), T, S, counts.numel(),
       perm.numel(), M, (int)KP, (int)off0, (int)off1, (int)thr,
       (const double*)bc_pow.data_ptr(), (float)lr, (float)b1, (float)b2,
-      (float)eps, (float)wd, cur_stream());
+      (float)eps, (float)wd, clear_counts ? 1 : 0, cur_stream());
+}
+
+void adam_table_bf16(torch::Tensor p, torch::Tensor gout, torch::Tensor perm,
+                     torch::Tensor counts, torch::Tensor cursor,
+                     torch::Tensor scratch, torch::Tensor master,
+                     torch::Tensor m, torch::Tensor v, torch::Tensor bc_pow,
+                     int64_t M, int64_t KP, int64_t off0, int64_t off1,
+                     int64_t thr, double lr, double b1, double b2, double eps,
+                     double wd) {
+  adam_table_bf16_impl(p, gout, perm, counts, cursor, scratch, master, m, v,
+                       bc_pow, M, KP, off0, off1, thr, lr, b1, b2, eps, wd,
+                       true);
+}
+
+// adam_table_bf16 that leaves the histogram in place: the caller clears both
+// tables' histograms with clear_i32_pair once both Adam kernels are queued.
+void adam_table_bf16_keep_counts(
+    torch::Tensor p, torch::Tensor gout, torch::Tensor perm,
+    torch::Tensor counts, torch::Tensor cursor, torch::Tensor scratch,
+    torch::Tensor master, torch::Tensor m, torch::Tensor v,
+    torch::Tensor bc_pow, int64_t M, int64_t KP, int64_t off0, int64_t off1,
+    int64_t thr, double lr, double b1, double b2, double eps, double wd) {
+  adam_table_bf16_impl(p, gout, perm, counts, cursor, scratch, master, m, v,
+                       bc_pow, M, KP, off0, off1, thr, lr, b1, b2, eps, wd,
+                       false);
+}
+
+// ---------------------------------------------------------------------------
+// Both embedding tables' counting sort in one chain (index_group.hip),
+// optionally on a side stream so it overlaps the forward and backward
+// kernels between the batch's arrival and the optimizer step.
+
+namespace {
+struct GroupStream {
+  hipStream_t side = nullptr;
+  hipEvent_t ready = nullptr;  // current stream -> side stream
+  hipEvent_t done = nullptr;   // side stream -> adopting/retiring stream
+};
+std::map<int, GroupStream>& group_streams() {
+  static std::map<int, GroupStream> m;
+  return m;
+}
+GroupStream& group_stream_for(int device) {
+  auto& m = group_streams();
+  auto it = m.find(device);
+  if (it == m.end()) {
+    // one stream from torch's pool for the life of the process
+    GroupStream g;
+    g.side = c10::hip::getStreamFromPool(false, device).stream();
+    C10_HIP_CHECK(hipEventCreateWithFlags(&g.ready, hipEventDisableTiming));
+    C10_HIP_CHECK(hipEventCreateWithFlags(&g.done, hipEventDisableTiming));
+    it = m.emplace(device, g).first;
+  }
+  return it->second;
+}
+void check_i32(const torch::Tensor& t, long n, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() &&
+                  t.scalar_type() == torch::kInt32 && t.numel() >= n,
+              "group_tables: ", what, " must be contiguous int32 on the GPU "
+              "with at least ", n, " elements");
+}
+}  // namespace
+
+// Returns true if the chain went to the side stream: the consumer must then
+// call group_tables_wait() on its stream before touching any output.  While
+// the current stream is capturing, or with side_stream false, the chain is
+// launched on the current stream.
+bool group_tables(torch::Tensor starts, torch::Tensor paths,
+                  torch::Tensor ends, torch::Tensor counts_t,
+                  torch::Tensor counts_p, torch::Tensor cursor_t,
+                  torch::Tensor cursor_p, torch::Tensor partial,
+                  torch::Tensor sorted_t, torch::Tensor perm_t,
+                  torch::Tensor sorted_p, torch::Tensor perm_p,
+                  int64_t rows_t, int64_t rows_p, bool side_stream) {
+  const long M = starts.numel();
+  TORCH_CHECK(M > 0 && 2 * M < (1L << 31), "group_tables: bad entry count");
+  TORCH_CHECK(rows_t > 0 && rows_p > 0 && rows_t < (1L << 31) &&
+                  rows_p < (1L << 31), "group_tables: bad histogram length");
+  check_i32(starts, M, "starts"); check_i32(paths, M, "paths");
+  check_i32(ends, M, "ends");
+  TORCH_CHECK(paths.numel() == M && ends.numel() == M,
+              "group_tables: starts/paths/ends sizes differ");
+  check_i32(counts_t, rows_t, "counts_t"); check_i32(counts_p, rows_p, "counts_p");
+  check_i32(cursor_t, rows_t, "cursor_t"); check_i32(cursor_p, rows_p, "cursor_p");
+  check_i32(partial, group_tables_partials(rows_t, rows_p), "partial");
+  check_i32(sorted_t, 2 * M, "sorted_t"); check_i32(sorted_p, M, "sorted_p");
+  CHK_CUDA(perm_t); CHK_CONTIG(perm_t); CHK_DT(perm_t, torch::kInt64);
+  CHK_CUDA(perm_p); CHK_CONTIG(perm_p); CHK_DT(perm_p, torch::kInt64);
+  TORCH_CHECK(perm_t.numel() >= 2 * M && perm_p.numel() >= M,
+              "group_tables: perm buffers too short");
+
+  auto cur = at::hip::getCurrentHIPStream();
+  hipStream_t launch_on = cur.stream();
+  bool on_side = false;
+  GroupStream* gs = nullptr;
+  if (side_stream) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    C10_HIP_CHECK(hipStreamIsCapturing(cur.stream(), &cap));
+    if (cap == hipStreamCaptureStatusNone) {
+      gs = &group_stream_for(cur.device_index());
+      // the side stream inherits everything the current stream is ordered
+      // after: the previous step's consumers of these buffers and whatever
+      // produced the indices
+      C10_HIP_CHECK(hipEventRecord(gs->ready, cur.stream()));
+      C10_HIP_CHECK(hipStreamWaitEvent(gs->side, gs->ready, 0));
+      launch_on = gs->side;
+      on_side = true;
+    }
+  }
+  launch_group_tables(
+      starts.data_ptr<int>(), paths.data_ptr<int>(), ends.data_ptr<int>(), M,
+      (int)rows_t, (int)rows_p, counts_t.data_ptr<int>(),
+      counts_p.data_ptr<int>(), cursor_t.data_ptr<int>(),
+      cursor_p.data_ptr<int>(), partial.data_ptr<int>(),
+      sorted_t.data_ptr<int>(), perm_t.data_ptr<long>(),
+      sorted_p.data_ptr<int>(), perm_p.data_ptr<long>(), launch_on);
+  if (on_side) C10_HIP_CHECK(hipEventRecord(gs->done, gs->side));
+  return on_side;
+}
+
+// Order the current stream after the latest side-stream group_tables chain.
+void group_tables_wait() {
+  auto cur = at::hip::getCurrentHIPStream();
+  auto& m = group_streams();
+  auto it = m.find(cur.device_index());
+  TORCH_CHECK(it != m.end(), "group_tables_wait: no side-stream grouping");
+  C10_HIP_CHECK(hipStreamWaitEvent(cur.stream(), it->second.done, 0));
+}
+
+int64_t group_tables_partials_len(int64_t rows_t, int64_t rows_p) {
+  return group_tables_partials(rows_t, rows_p);
+}
+
+// embed_scatter_heavy for both tables of one group_tables record pair:
+// gout [M, KP] = [start (S_t) | path (S_p) | end (S_t) | pad].
+void embed_scatter_heavy_pair(torch::Tensor sorted_t, torch::Tensor perm_t,
+                              torch::Tensor counts_t, torch::Tensor dtable_t,
+                              torch::Tensor sorted_p, torch::Tensor perm_p,
+                              torch::Tensor counts_p, torch::Tensor dtable_p,
+                              torch::Tensor gout, int64_t M, int64_t KP,
+                              int64_t thr) {
+  CHK_DT(dtable_t, torch::kFloat32); CHK_CONTIG(dtable_t);
+  CHK_DT(dtable_p, torch::kFloat32); CHK_CONTIG(dtable_p);
+  TORCH_CHECK(dtable_t.dim() == 2 && dtable_p.dim() == 2,
+              "dtable must be [T, S]");
+  const int St = dtable_t.size(1), Sp = dtable_p.size(1);
+  check_table_record(perm_t.narrow(0, 0, 2 * M), counts_t, gout,
+                     dtable_t.size(0), St, M, KP, 0, St + Sp);
+  check_table_record(perm_p.narrow(0, 0, M), counts_p, gout,
+                     dtable_p.size(0), Sp, M, KP, St, St);
+  check_i32(sorted_t, 2 * M, "sorted_t"); check_i32(sorted_p, M, "sorted_p");
+  TORCH_CHECK(St % 2 == 0 && Sp % 2 == 0 && St <= 512 && Sp <= 512 &&
+                  KP % 2 == 0, "embed_scatter_heavy_pair: S/KP alignment");
+  TORCH_CHECK(thr >= 32, "embed_scatter_heavy_pair: thr must be >= 32");
+  launch_embed_scatter_heavy_pair(
+      sorted_t.data_ptr<int>(), perm_t.data_ptr<long>(),
+      counts_t.data_ptr<int>(), dtable_t.data_ptr<float>(), St,
+      sorted_p.data_ptr<int>(), perm_p.data_ptr<long>(),
+      counts_p.data_ptr<int>(), dtable_p.data_ptr<float>(), Sp,
+      gout.data_ptr(), M, (int)KP, (int)thr, cur_stream());
+}
+
+void clear_i32_pair(torch::Tensor a, torch::Tensor b) {
+  check_i32(a, 0, "a"); check_i32(b, 0, "b");
+  launch_clear_i32_pair(a.data_ptr<int>(), a.numel(), b.data_ptr<int>(),
+                        b.numel(), cur_stream());
 }
 
 void adam_step_f32(torch::Tensor p, torch::Tensor g, torch::Tensor m,
@@ -1161,4 +1340,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("embed_scatter_heavy", &embed_scatter_heavy);
   m.def("adam_table_bf16", &adam_table_bf16);
   m.def("adam_step_f32_multi", &adam_step_f32_multi);
+  m.def("adam_table_bf16_keep_counts", &adam_table_bf16_keep_counts);
+  m.def("group_tables", &group_tables);
+  m.def("group_tables_wait", &group_tables_wait);
+  m.def("group_tables_partials_len", &group_tables_partials_len);
+  m.def("embed_scatter_heavy_pair", &embed_scatter_heavy_pair);
+  m.def("clear_i32_pair", &clear_i32_pair);
 }

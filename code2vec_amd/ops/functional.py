@@ -94,6 +94,17 @@ OWNED_GRAD_KEYS = set()
 # row is pre-reduced into the fp32 scratch instead of gathered in-kernel.
 DEFERRED_GRAD_KEYS = set()
 _TABLE_ADAM_HEAVY = int(os.environ.get("C2V_TABLE_ADAM_HEAVY", "64"))
+# Where both tables are deferred, one group_tables chain (index_group.hip)
+# groups both index lists at FORWARD time — they depend on the batch only —
+# and the backward adopts the result (see _launch_table_grouping).
+# C2V_GROUP_TABLES=0 keeps the per-table chain inside backward.
+# C2V_GROUP_STREAM=1 launches the merged chain on a side stream so that it
+# overlaps the step; measured SLOWER than launching it on the forward's own
+# stream (1.160-1.176 against 1.128-1.136 ms/step at top11, parent
+# 1.151-1.158: the two cross-stream waits cost more than the ~75 us chain
+# they hide, see PERF.md), so it is off by default.
+_GROUP_TABLES = os.environ.get("C2V_GROUP_TABLES", "1") == "1"
+_GROUP_STREAM = os.environ.get("C2V_GROUP_STREAM", "0") == "1"
 
 from . import ext, round_up
 
@@ -127,8 +138,15 @@ class GatherConcat(torch.autograd.Function):
     out[b*C+c] = [term[starts] (TS cols) | path[paths] (PS) | term[ends] (TS)]
     """
 
+    @classmethod
+    def apply(cls, starts, paths, ends, term_w, path_w, training=True):
+        # forward() itself always runs with grad mode off: whether a
+        # backward can follow is only visible out here
+        track = bool(training) and torch.is_grad_enabled()
+        return super().apply(starts, paths, ends, term_w, path_w, track)
+
     @staticmethod
-    def forward(ctx, starts, paths, ends, term_w, path_w):
+    def forward(ctx, starts, paths, ends, term_w, path_w, track=False):
         B, C = starts.shape
         TS = term_w.shape[1]
         PS = path_w.shape[1]
@@ -136,6 +154,11 @@ class GatherConcat(torch.autograd.Function):
             B * C, round_up(2 * TS + PS, 32), dtype=torch.bfloat16,
             device=starts.device
         )
+        # the grouping goes first so that, on its side stream, it runs
+        # under the gather and everything after it
+        ctx.group_ticket = (
+            _launch_table_grouping(starts, paths, ends, term_w, path_w)
+            if track else None)
         ext().gather_concat_fwd(starts, paths, ends, term_w, path_w, out)
         ctx.save_for_backward(starts, paths, ends)
         ctx.shapes = (term_w.shape, path_w.shape)
@@ -148,13 +171,15 @@ class GatherConcat(torch.autograd.Function):
         term_shape, path_shape = ctx.shapes
         dterm, dpath = _scatter_embedding_grads(
             starts, paths, ends, grad_out.contiguous(), term_shape,
-            path_shape, ctx.param_keys[0], ctx.param_keys[1]
+            path_shape, ctx.param_keys[0], ctx.param_keys[1],
+            ticket=ctx.group_ticket
         )
-        return None, None, None, dterm, dpath
+        return None, None, None, dterm, dpath, None
 
 
 def _scatter_embedding_grads(starts, paths, ends, gout, term_shape,
-                             path_shape, term_key=None, path_key=None):
+                             path_shape, term_key=None, path_key=None,
+                             ticket=None):
     """K13 v4: sort-based segmented scatter of a [M, KP] grad into bf16
     dense embedding grads.  Counting-sort groups the index lists; run-owner
     waves write interior rows' bf16 grads directly; boundary-crossing runs
@@ -163,10 +188,32 @@ def _scatter_embedding_grads(starts, paths, ends, gout, term_shape,
 
     Deferred form: for an owned key listed in DEFERRED_GRAD_KEYS only the
     grouping runs; the owner's callback gets a DeferredTableGrad record and
-    autograd gets None (see table_adam_deferred)."""
+    autograd gets None (see table_adam_deferred).  ``ticket`` names the
+    grouping the forward launched for this batch (_launch_table_grouping):
+    if it is the outstanding one, both records come from it and nothing is
+    grouped here."""
     M = starts.numel()
     TS, PS = term_shape[1], path_shape[1]
     KP = gout.shape[1]
+
+    grouping = _adopt_table_grouping(ticket, M, term_shape, path_shape,
+                                     term_key, path_key)
+    if grouping is not None:
+        pair = _GroupedPair()
+        for tag, shape, key, off0, off1 in (
+                ("term", term_shape, term_key, 0, TS + PS),
+                ("path", path_shape, path_key, TS, TS)):
+            sorted_idx, perm, counts, cursor = grouping.tables[tag]
+            rec = DeferredTableGrad(tag, gout, perm, counts, cursor,
+                                    sorted_idx, M, KP, off0, off1,
+                                    tuple(shape))
+            rec.pair = pair
+            pair.recs[tag] = rec
+            _PENDING_DEFERRED[counts.data_ptr()] = rec
+        # term first, as in the per-table chain below
+        EARLY_GRAD_CALLBACKS[term_key](pair.recs["term"])
+        EARLY_GRAD_CALLBACKS[path_key](pair.recs["path"])
+        return None, None
 
     def one_table(tag, idx, shape, key, off0, off1):
         sorted_idx, perm, counts, cursor = _group_by_index(
@@ -206,7 +253,7 @@ class DeferredTableGrad:
     ``gout`` stays alive through the record until then."""
 
     __slots__ = ("tag", "gout", "perm", "counts", "cursor", "sorted_idx",
-                 "M", "KP", "off0", "off1", "shape", "consumed")
+                 "M", "KP", "off0", "off1", "shape", "consumed", "pair")
 
     def __init__(self, tag, gout, perm, counts, cursor, sorted_idx, M, KP,
                  off0, off1, shape):
@@ -215,6 +262,7 @@ class DeferredTableGrad:
         self.M, self.KP, self.off0, self.off1 = M, KP, off0, off1
         self.shape = shape
         self.consumed = False
+        self.pair = None  # _GroupedPair of a group_tables record
 
     def _consume(self):
         if self.consumed:
@@ -233,11 +281,44 @@ class DeferredTableGrad:
 _PENDING_DEFERRED = {}
 
 
+class _GroupedPair:
+    """The two records of one group_tables call.  While both go through
+    table_adam_deferred, the heavy-row pre-pass runs once for both tables
+    (before the first Adam) and both histograms are cleared in one launch
+    (after the second Adam: several threads of an Adam kernel read each
+    row's count, so no clear may overtake it).  A record consumed any other
+    way breaks the pair (_leave_pair) and what is left runs per table."""
+
+    __slots__ = ("recs", "prepassed", "stepped", "broken")
+
+    def __init__(self):
+        self.recs = {}
+        self.prepassed = False
+        self.stepped = []
+        self.broken = False
+
+
+def _leave_pair(rec: "DeferredTableGrad") -> None:
+    """``rec`` is about to be materialized or discarded, not stepped."""
+    pair = rec.pair
+    if pair is None:
+        return
+    if pair.prepassed:
+        # its heavy rows sit in the scratch for an Adam that will not run
+        _scratch_f32(rec.tag, rec.shape, rec.counts.device).zero_()
+    if not pair.broken:
+        pair.broken = True
+        # an Adam that already ran left its histogram for the merged clear
+        for other in pair.stepped:
+            other.counts.zero_()
+
+
 def materialize_deferred(rec: DeferredTableGrad) -> torch.Tensor:
     """Dense bf16 gradient table from a record: the sorted scatter plus
     cast_clear_rows (which consumes counts/flags and re-zeroes the fp32
     scratch rows it read)."""
     rec._consume()
+    _leave_pair(rec)
     dev = rec.gout.device
     d32 = _scratch_f32(rec.tag, rec.shape, dev)
     flags = _scratch_flags(rec.tag, rec.shape[0], dev)
@@ -257,6 +338,7 @@ def discard_deferred(rec: DeferredTableGrad) -> None:
     if rec.consumed:
         return
     rec._consume()
+    _leave_pair(rec)
     rec.counts.zero_()
     rec._release()
 
@@ -270,14 +352,141 @@ def table_adam_deferred(param, master, m, v, rec: DeferredTableGrad, bc_pow,
     rec._consume()
     assert tuple(param.shape) == rec.shape and master is not None
     scratch = _scratch_f32(rec.tag, rec.shape, param.device)
-    ext().embed_scatter_heavy(rec.sorted_idx, rec.perm, rec.counts, rec.gout,
-                              scratch, rec.M, rec.KP, rec.off0, rec.off1,
-                              _TABLE_ADAM_HEAVY)
+    pair = rec.pair
+    if pair is not None and not pair.broken:
+        # records of one group_tables call: one pre-pass and one clear for
+        # both tables
+        t, p = pair.recs["term"], pair.recs["path"]
+        if not pair.prepassed:
+            ext().embed_scatter_heavy_pair(
+                t.sorted_idx, t.perm, t.counts,
+                _scratch_f32("term", t.shape, param.device),
+                p.sorted_idx, p.perm, p.counts,
+                _scratch_f32("path", p.shape, param.device),
+                rec.gout, rec.M, rec.KP, _TABLE_ADAM_HEAVY)
+            pair.prepassed = True
+        ext().adam_table_bf16_keep_counts(
+            param, rec.gout, rec.perm, rec.counts, rec.cursor, scratch,
+            master, m, v, bc_pow, rec.M, rec.KP, rec.off0, rec.off1,
+            _TABLE_ADAM_HEAVY, lr, beta1, beta2, eps, weight_decay)
+        pair.stepped.append(rec)
+        if len(pair.stepped) == 2:
+            ext().clear_i32_pair(t.counts, p.counts)
+            pair.recs = {}
+        rec._release()
+        return
+    if pair is None or not pair.prepassed:
+        ext().embed_scatter_heavy(rec.sorted_idx, rec.perm, rec.counts,
+                                  rec.gout, scratch, rec.M, rec.KP, rec.off0,
+                                  rec.off1, _TABLE_ADAM_HEAVY)
     ext().adam_table_bf16(param, rec.gout, rec.perm, rec.counts, rec.cursor,
                           scratch, master, m, v, bc_pow, rec.M, rec.KP,
                           rec.off0, rec.off1, _TABLE_ADAM_HEAVY, lr, beta1,
                           beta2, eps, weight_decay)
     rec._release()
+
+
+class _TableGrouping:
+    """One group_tables call whose records no backward has taken yet."""
+
+    __slots__ = ("ticket", "index_tensors", "tables", "on_side", "M",
+                 "shapes", "keys")
+
+
+_group_state = {"outstanding": None, "next_ticket": 1}
+
+
+def _grouping_applies(term_key, path_key) -> bool:
+    return all(k is not None and k in OWNED_GRAD_KEYS
+               and k in DEFERRED_GRAD_KEYS and k in EARLY_GRAD_CALLBACKS
+               for k in (term_key, path_key))
+
+
+def _launch_table_grouping(starts, paths, ends, term_w, path_w):
+    """Group both tables' indices for the backward of this forward and
+    return the ticket that backward adopts them with, or None where the
+    deferred table gradient does not apply (then backward groups per table
+    as before).  At most one grouping is outstanding: one that no backward
+    adopted is retired first."""
+    if not (_GROUP_TABLES and starts.is_cuda and term_w.requires_grad
+            and path_w.requires_grad
+            and _grouping_applies(term_w.data_ptr(), path_w.data_ptr())
+            and starts.dtype == paths.dtype == ends.dtype == torch.int32
+            and starts.is_contiguous() and paths.is_contiguous()
+            and ends.is_contiguous() and starts.numel() > 0):
+        return None
+    retire_table_grouping()
+    dev = starts.device
+    M = starts.numel()
+    g = _TableGrouping()
+    g.tables = {}
+    bufs = {}
+    for tag, rows, n in (("term", term_w.shape[0] + 1, 2 * M),
+                         ("path", path_w.shape[0] + 1, M)):
+        counts = _scratch_i32(f"counts_{tag}", rows, dev)
+        # a deferred record nobody consumed still holds its histogram here
+        stale = _PENDING_DEFERRED.get(counts.data_ptr())
+        if stale is not None:
+            discard_deferred(stale)
+        cursor = _scratch_i32(f"cursor_{tag}", rows, dev, zero=False)
+        sorted_idx = _scratch_i32(f"gsorted_{tag}", n, dev, zero=False)
+        perm = _scratch_i64(f"gperm_{tag}", n, dev)
+        g.tables[tag] = (sorted_idx, perm, counts, cursor)
+        bufs[tag] = rows
+    spart = _scratch_i32(
+        "gscanp", int(ext().group_tables_partials_len(bufs["term"],
+                                                      bufs["path"])),
+        dev, zero=False)
+    st, sp = g.tables["term"], g.tables["path"]
+    g.on_side = bool(ext().group_tables(
+        starts, paths, ends, st[2], sp[2], st[3], sp[3], spart, st[0], st[1],
+        sp[0], sp[1], bufs["term"], bufs["path"], _GROUP_STREAM))
+    # the side-stream kernels read these: they stay alive here until a
+    # backward adopts the grouping (whose ctx holds them too) or it is
+    # retired, both of which order the current stream after the kernels
+    g.index_tensors = (starts, paths, ends)
+    g.M = M
+    g.shapes = (tuple(term_w.shape), tuple(path_w.shape))
+    g.keys = (term_w.data_ptr(), path_w.data_ptr())
+    g.ticket = _group_state["next_ticket"]
+    _group_state["next_ticket"] += 1
+    _group_state["outstanding"] = g
+    return g.ticket
+
+
+def _adopt_table_grouping(ticket, M, term_shape, path_shape, term_key,
+                          path_key):
+    """The outstanding grouping if ``ticket`` names it and it still fits
+    this backward, with the current stream ordered after its kernels; else
+    None, after retiring whatever was outstanding."""
+    g = _group_state["outstanding"]
+    if g is None:
+        return None
+    if (ticket is None or g.ticket != ticket or g.M != M
+            or g.shapes != (tuple(term_shape), tuple(path_shape))
+            or g.keys != (term_key, path_key)
+            or not _grouping_applies(term_key, path_key)):
+        retire_table_grouping()
+        return None
+    _group_state["outstanding"] = None
+    if g.on_side:
+        ext().group_tables_wait()
+    return g
+
+
+def retire_table_grouping() -> None:
+    """Drop a grouping no backward adopted (a training forward without a
+    backward, a second forward before the first backward): wait for its
+    kernels and re-zero both histograms, which is all it wrote that carries
+    an invariant."""
+    g = _group_state["outstanding"]
+    if g is None:
+        return
+    _group_state["outstanding"] = None
+    if g.on_side:
+        ext().group_tables_wait()
+    for tag in ("term", "path"):
+        g.tables[tag][2].zero_()
 
 
 _scratch_cache = {}
@@ -313,6 +522,16 @@ def _scratch_i32(tag: str, n: int, device, zero: bool = True) -> torch.Tensor:
     if buf is None:
         maker = torch.zeros if zero else torch.empty
         buf = maker(n, dtype=torch.int32, device=device)
+        _scratch_cache[key] = buf
+    return buf
+
+
+def _scratch_i64(tag: str, n: int, device) -> torch.Tensor:
+    """Persistent int64 scratch (fully overwritten by its producer)."""
+    key = ("i64", tag, n, str(device))
+    buf = _scratch_cache.get(key)
+    if buf is None:
+        buf = torch.empty(n, dtype=torch.int64, device=device)
         _scratch_cache[key] = buf
     return buf
 
@@ -408,6 +627,8 @@ def _group_by_index(idx: torch.Tensor, table_rows: int,
     N = idx.numel()
     dev = idx.device
     if pool_tag is not None:
+        # a forward-time grouping nobody adopted may hold this histogram
+        retire_table_grouping()
         counts = _scratch_i32(f"counts_{pool_tag}", table_rows + 1, dev)
         # a deferred record nobody consumed (backward without a step)
         # still holds its histogram in this buffer

@@ -290,6 +290,8 @@ class BucketedAllReduce:
             p.grad = None
         for b in self.buckets:
             b.flat.zero_()
+        # a forward-time table grouping no backward adopted
+        Fn.retire_table_grouping()
         self._reset_pending()
 
     def broadcast_parameters(self) -> None:
@@ -301,6 +303,7 @@ class BucketedAllReduce:
     def close(self) -> None:
         """Deregister the owned-grad callbacks (test hygiene: a later
         BucketedAllReduce on the same model replaces them anyway)."""
+        Fn.retire_table_grouping()
         for p in self.owned_params:
             key = p.data_ptr()
             Fn.OWNED_GRAD_KEYS.discard(key)

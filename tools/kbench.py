@@ -7,8 +7,10 @@ env vars read by ops/functional.py.  Usage (on a GPU box):
 ``row_topk`` (K19 vs torch.topk + torch.logsumexp), ``table_adam``
 (scatter + cast_clear + adam_bf16 vs the row-gathering table Adam) and
 ``bwd_fusions`` (one-launch reductions, compact attention backward and
-recomputing combiner backward vs what they replace) are not in the default
-set; asked for alone they skip building the model-shaped operands.
+recomputing combiner backward vs what they replace) and ``group_tables``
+(both tables' counting sort: per-table chains vs the one merged chain) are
+not in the default set; asked for alone they skip building the model-shaped
+operands.
 """
 
 from __future__ import annotations
@@ -145,6 +147,65 @@ def bench_table_adam(dev, results, rounds=5):
         print(f"# table_adam {tag}: {gbs:.0f} GB/s effective (median, new)")
 
 
+def bench_group_tables(dev, results, rounds=5):
+    """Counting sort of both tables' index lists, old against new on the
+    SAME persistent buffers, alternating within each round (median / min):
+      old: torch.cat + per table count, scan, scatter_group (13 launches
+           with the two histogram clears the table Adam pays afterwards)
+      new: group_tables on the current stream + clear_i32_pair (5 launches)
+    at the top11 shapes with uniform indices over [1, rows) and with a
+    ragged batch (half <PAD/>).  Both variants leave the histograms zero."""
+    from code2vec_amd.ops import ext
+
+    M, T, P = 1024 * 200, 360632, 342846
+    g = torch.Generator(device=dev).manual_seed(0)
+    for tag in ("uniform", "half-pad"):
+        starts = torch.randint(1, T, (1024, 200), generator=g, device=dev,
+                               dtype=torch.int32)
+        paths = torch.randint(1, P, (1024, 200), generator=g, device=dev,
+                              dtype=torch.int32)
+        ends = torch.randint(1, T, (1024, 200), generator=g, device=dev,
+                             dtype=torch.int32)
+        if tag == "half-pad":
+            for t in (starts, paths, ends):
+                t[:, 100:] = 0
+        bufs = {}
+        for name, rows, n in (("term", T + 1, 2 * M), ("path", P + 1, M)):
+            bufs[name] = (
+                Fn._scratch_i32(f"gsorted_{name}", n, dev, zero=False),
+                Fn._scratch_i64(f"gperm_{name}", n, dev),
+                Fn._scratch_i32(f"counts_{name}", rows, dev),
+                Fn._scratch_i32(f"cursor_{name}", rows, dev, zero=False))
+        spart = Fn._scratch_i32(
+            "gscanp", int(ext().group_tables_partials_len(T + 1, P + 1)),
+            dev, zero=False)
+        bt, bp = bufs["term"], bufs["path"]
+
+        def old():
+            idx_se = torch.cat([starts.view(-1), ends.view(-1)])
+            a = Fn._group_by_index(idx_se, T, pool_tag="term",
+                                   with_cursor=True)
+            b = Fn._group_by_index(paths.view(-1), P, pool_tag="path",
+                                   with_cursor=True)
+            a[2].zero_()
+            b[2].zero_()
+
+        def new():
+            ext().group_tables(starts, paths, ends, bt[2], bp[2], bt[3],
+                               bp[3], spart, bt[0], bt[1], bp[0], bp[1],
+                               T + 1, P + 1, False)
+            ext().clear_i32_pair(bt[2], bp[2])
+
+        t = {"old": [], "new": []}
+        for _ in range(rounds):
+            t["old"].append(timeit(old, iters=50))
+            t["new"].append(timeit(new, iters=50))
+        for name, vals in t.items():
+            vals.sort()
+            results[f"group_tables({tag}) {name} med"] = vals[rounds // 2]
+            results[f"group_tables({tag}) {name} min"] = vals[0]
+
+
 def bench_bwd_fusions(dev, results, rounds=5):
     """The one-launch reductions against what they replace on the SAME
     buffers, alternating within each round (median / min), at top11 shapes:
@@ -228,13 +289,16 @@ def main():
         print("kbench: needs a GPU (per-kernel timing); run under gpurun")
         return
     dev = torch.device("cuda:0")
-    if sys.argv[1:] in (["row_topk"], ["table_adam"], ["bwd_fusions"]):
+    if sys.argv[1:] in (["row_topk"], ["table_adam"], ["bwd_fusions"],
+                        ["group_tables"]):
         # needs none of the model-shaped operands built below
         results = {}
         if sys.argv[1] == "row_topk":
             bench_row_topk(dev, results)
         elif sys.argv[1] == "bwd_fusions":
             bench_bwd_fusions(dev, results)
+        elif sys.argv[1] == "group_tables":
+            bench_group_tables(dev, results)
         else:
             bench_table_adam(dev, results)
         for k, vv in results.items():
@@ -432,6 +496,8 @@ def main():
         bench_row_topk(dev, results)
     if "table_adam" in ops:
         bench_table_adam(dev, results)
+    if "group_tables" in ops:
+        bench_group_tables(dev, results)
 
     for k, vv in results.items():
         print(f"{k:24s} {vv:10.1f} us")
