@@ -54,6 +54,11 @@ void launch_combiner_fwd(const void*, const void*, const float*, const float*,
                          void*, void*, float*, float*, long, int, int, int,
                          float, unsigned long long,
                          const unsigned long long*, int, hipStream_t);
+int launch_combiner_fwd_scores(const void*, const void*, const float*,
+                               const float*, void*, void*, float*, float*,
+                               long, int, int, int, float, unsigned long long,
+                               const unsigned long long*, int, const float*,
+                               float*, hipStream_t);
 void launch_bump_u64(void*, unsigned long long, hipStream_t);
 void launch_gather_combiner_fwd(const int*, const int*, const int*,
                                 const void*, const void*, int, int,
@@ -78,6 +83,14 @@ void launch_attention_bwd(const void*, int, const float*, const void*,
                           const float*, const int*, const float*, void*,
                           float*, float*, int, int, int, int, int,
                           hipStream_t);
+int attention_stream_supported(int, int);
+void launch_attention_fwd_scores(const void*, const float*, const int*,
+                                 float*, void*, float*, int, int, int, int,
+                                 hipStream_t);
+void launch_attention_bwd_compact_reg(const void*, int, const float*,
+                                      const void*, const int*, const float*,
+                                      float*, float*, int, int, int, int, int,
+                                      hipStream_t);
 void launch_slab_sum2_f32(const float*, const float*, float*, float*, int,
                           int, hipStream_t);
 void launch_loss_reduce(const float*, float*, float*, int, hipStream_t);
@@ -241,6 +254,49 @@ void combiner_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor gamma,
                     cur_stream());
 }
 
+// combiner_fwd that also emits the attention pool's raw scores
+// raw_scores[M] = out . a from its flush (EP = 128, staged epilogue).
+// Returns false, with raw_scores untouched, when the shape or epilogue
+// mode has no score-emitting kernel; out/z/mean/rstd are written either
+// way, with the bits of combiner_fwd.
+bool combiner_fwd_scores(torch::Tensor x, torch::Tensor w,
+                         torch::Tensor gamma, torch::Tensor beta,
+                         torch::Tensor a, torch::Tensor out, torch::Tensor z,
+                         torch::Tensor mean, torch::Tensor rstd,
+                         torch::Tensor raw_scores, int64_t E, double p,
+                         int64_t seed, torch::Tensor rng_off,
+                         int64_t epilogue_mode) {
+  CHK_CUDA(x); CHK_CONTIG(x); CHK_DT(x, torch::kBFloat16);
+  CHK_CONTIG(w); CHK_DT(w, torch::kBFloat16);
+  CHK_DT(gamma, torch::kFloat32); CHK_DT(beta, torch::kFloat32);
+  CHK_DT(out, torch::kBFloat16); CHK_DT(z, torch::kBFloat16);
+  CHK_CONTIG(out); CHK_CONTIG(z);
+  CHK_DT(mean, torch::kFloat32); CHK_DT(rstd, torch::kFloat32);
+  CHK_CUDA(a); CHK_CONTIG(a); CHK_DT(a, torch::kFloat32);
+  CHK_CUDA(raw_scores); CHK_CONTIG(raw_scores);
+  CHK_DT(raw_scores, torch::kFloat32);
+  const long M = x.size(0);
+  const int KP = x.size(1), EP = w.size(0);  // w is TRANSPOSED: [EP, KP]
+  TORCH_CHECK(w.size(1) == KP && KP % 32 == 0 && EP % 32 == 0, "w shape");
+  TORCH_CHECK(a.numel() == EP && raw_scores.numel() == M &&
+              out.numel() == M * EP && z.numel() == M * EP &&
+              mean.numel() == M && rstd.numel() == M &&
+              gamma.numel() == EP && beta.numel() == EP,
+              "combiner_fwd_scores shapes");
+  CHK_DT(rng_off, torch::kInt64);
+  const int wrote = launch_combiner_fwd_scores(
+      x.data_ptr(), w.data_ptr(), gamma.data_ptr<float>(),
+      beta.data_ptr<float>(), out.data_ptr(), z.data_ptr(),
+      mean.data_ptr<float>(), rstd.data_ptr<float>(), M, KP, EP, (int)E,
+      (float)p, (unsigned long long)seed,
+      (const unsigned long long*)rng_off.data_ptr(), (int)epilogue_mode,
+      a.data_ptr<float>(), raw_scores.data_ptr<float>(), cur_stream());
+  if (p > 0.0)
+    launch_bump_u64(rng_off.data_ptr(), (unsigned long long)(M * EP),
+                    cur_stream());
+  return wrote != 0;
+}
+
 void gather_combiner_fwd(torch::Tensor starts, torch::Tensor paths,
                          torch::Tensor ends, torch::Tensor term,
                          torch::Tensor path, torch::Tensor w,
@@ -382,6 +438,72 @@ void attention_bwd_compact(torch::Tensor dcv, torch::Tensor dattn,
                        starts.data_ptr<int>(), attn.data_ptr<float>(),
                        nullptr, ds.data_ptr<float>(), da.data_ptr<float>(),
                        B, C, EP, (int)E, has_dattn ? 1 : 0, cur_stream());
+}
+
+// shape gate of the two streaming attention kernels below
+bool attention_stream_ok(int64_t C, int64_t EP) {
+  return attention_stream_supported((int)C, (int)EP) != 0;
+}
+
+// attention forward from precomputed raw scores [B*C] (combiner_fwd_scores):
+// mask, softmax, weighted pool; writes cv, cvb (bf16 copy) and attn
+void attention_fwd_scores(torch::Tensor ccv, torch::Tensor raw_scores,
+                          torch::Tensor starts, torch::Tensor cv,
+                          torch::Tensor cvb, torch::Tensor attn, int64_t E) {
+  CHK_CUDA(ccv); CHK_CONTIG(ccv); CHK_DT(ccv, torch::kBFloat16);
+  CHK_CUDA(raw_scores); CHK_CONTIG(raw_scores);
+  CHK_DT(raw_scores, torch::kFloat32);
+  CHK_DT(cv, torch::kFloat32); CHK_CONTIG(cv);
+  CHK_DT(cvb, torch::kBFloat16); CHK_CONTIG(cvb);
+  CHK_DT(attn, torch::kFloat32); CHK_CONTIG(attn);
+  CHK_DT(starts, torch::kInt32); CHK_CONTIG(starts);
+  TORCH_CHECK(ccv.dim() == 3, "ccv must be [B, C, EP]");
+  const int B = ccv.size(0), C = ccv.size(1), EP = ccv.size(2);
+  TORCH_CHECK(attention_stream_supported(C, EP),
+              "attention_fwd_scores: needs EP = 128 and 1 <= C <= 200");
+  TORCH_CHECK(E >= 1 && E <= EP && raw_scores.numel() == (long)B * C &&
+              cv.numel() == (long)B * EP && cvb.numel() == (long)B * EP &&
+              attn.numel() == (long)B * C && starts.numel() == (long)B * C,
+              "attention_fwd_scores shapes");
+  launch_attention_fwd_scores(ccv.data_ptr(), raw_scores.data_ptr<float>(),
+                              starts.data_ptr<int>(), cv.data_ptr<float>(),
+                              cvb.data_ptr(), attn.data_ptr<float>(), B, C,
+                              EP, (int)E, cur_stream());
+}
+
+// attention_bwd_compact with the method's rows held in registers
+// (EP = 128, C <= 200); same outputs, same bits
+void attention_bwd_compact_reg(torch::Tensor dcv, torch::Tensor dattn,
+                               torch::Tensor ccv, torch::Tensor starts,
+                               torch::Tensor attn, torch::Tensor ds,
+                               torch::Tensor da, int64_t E, bool has_dattn) {
+  CHK_CUDA(dcv); CHK_CONTIG(dcv); CHK_CUDA(ccv); CHK_CONTIG(ccv);
+  CHK_DT(ccv, torch::kBFloat16);
+  const bool dcv_bf16 = dcv.scalar_type() == torch::kBFloat16;
+  TORCH_CHECK(dcv_bf16 || dcv.scalar_type() == torch::kFloat32,
+              "dcv must be f32 or bf16");
+  CHK_DT(ds, torch::kFloat32); CHK_CONTIG(ds);
+  CHK_DT(da, torch::kFloat32); CHK_CONTIG(da);
+  CHK_DT(attn, torch::kFloat32); CHK_CONTIG(attn);
+  CHK_DT(starts, torch::kInt32); CHK_CONTIG(starts);
+  TORCH_CHECK(ccv.dim() == 3, "ccv must be [B, C, EP]");
+  const int B = ccv.size(0), C = ccv.size(1), EP = ccv.size(2);
+  TORCH_CHECK(attention_stream_supported(C, EP),
+              "attention_bwd_compact_reg: needs EP = 128 and 1 <= C <= 200");
+  TORCH_CHECK(E >= 1 && E <= EP && dcv.numel() == (long)B * EP &&
+              ds.numel() == (long)B * C && da.numel() == (long)B * EP &&
+              attn.numel() == (long)B * C && starts.numel() == (long)B * C,
+              "attention_bwd_compact_reg shapes");
+  if (has_dattn) {
+    CHK_DT(dattn, torch::kFloat32); CHK_CONTIG(dattn);
+    TORCH_CHECK(dattn.numel() == (long)B * C, "dattn shape");
+  }
+  launch_attention_bwd_compact_reg(
+      dcv.data_ptr(), dcv_bf16 ? 1 : 0,
+      has_dattn ? dattn.data_ptr<float>() : nullptr, ccv.data_ptr(),
+      starts.data_ptr<int>(), attn.data_ptr<float>(), ds.data_ptr<float>(),
+      da.data_ptr<float>(), B, C, EP, (int)E, has_dattn ? 1 : 0,
+      cur_stream());
 }
 
 // combiner backward that rebuilds dout = bf16(attn*dcv + ds*a) in
@@ -1299,6 +1421,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attention_bwd", &attention_bwd);
   m.def("attention_fwd_cvb", &attention_fwd_cvb);
   m.def("attention_bwd_compact", &attention_bwd_compact);
+  m.def("combiner_fwd_scores", &combiner_fwd_scores);
+  m.def("attention_stream_ok", &attention_stream_ok);
+  m.def("attention_fwd_scores", &attention_fwd_scores);
+  m.def("attention_bwd_compact_reg", &attention_bwd_compact_reg);
   m.def("combiner_bwd_recompute", &combiner_bwd_recompute);
   m.def("slab_sum2_f32", &slab_sum2_f32);
   m.def("loss_reduce", &loss_reduce);

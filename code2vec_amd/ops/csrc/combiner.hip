@@ -43,7 +43,13 @@
 // must honor (occupancy experiment C2V_COMBINER_OCC — the default NT=8/MT=2
 // build lands at 230 VGPR+AGPR = 2 waves/SIMD; forcing 3 trades ILP/spill
 // for latency hiding on the TA-issue-bound A-fragment loads).
-template <int NT, int EPI, int GATHER, int MT = 2, int MINW = 1>
+// SCORES=1 (NT = 8, EPI = 1 only): the flush of `out` also emits the
+// attention pool's raw scores, raw_scores[row] = out[row] . att_a — the
+// flush already holds each row as 16 lanes x 8 columns, the mapping of
+// attention_fwd_kernel's phase 1, so the pool's forward never has to read
+// `out` for its scores (attention_fwd_scores_kernel).
+template <int NT, int EPI, int GATHER, int MT = 2, int MINW = 1,
+          int SCORES = 0>
 __global__ __launch_bounds__(256, MINW) void combiner_fwd_kernel(
     const bf16* __restrict__ X, const bf16* __restrict__ Wt,
     const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -53,7 +59,9 @@ __global__ __launch_bounds__(256, MINW) void combiner_fwd_kernel(
     unsigned long long seed, const unsigned long long* __restrict__ rng_off,
     const int* __restrict__ g_starts, const int* __restrict__ g_paths,
     const int* __restrict__ g_ends, const bf16* __restrict__ g_term,
-    const bf16* __restrict__ g_path, int TS, int PS) {
+    const bf16* __restrict__ g_path, int TS, int PS,
+    const float* __restrict__ att_a, float* __restrict__ raw_scores) {
+  static_assert(!SCORES || (NT == 8 && EPI == 1), "scores need EP=128, EPI=1");
   const int EP = NT * 16;
   const int lane = threadIdx.x & (WAVE - 1);
   const int wave = threadIdx.x / WAVE;
@@ -247,7 +255,32 @@ __global__ __launch_bounds__(256, MINW) void combiner_fwd_kernel(
         }
       }
     }
-    if (EPI == 1) {
+    if (EPI == 1 && SCORES && pass == 1) {
+      // flush `out` and dot each row with att_a on the way: per iteration
+      // a 16-lane group holds one row (row_l = it*4 + lane/16), a lane its
+      // columns col8..col8+7 — group_row_dot's mapping at EP = 128.  The
+      // 8 floats of att_a are loaded here, after the K-loop, where the
+      // accumulators are dead.  Columns >= round8(E) contribute 0, as in
+      // the attention kernels; the mask is applied by the consumer.
+      const int col8 = (lane & 15) * 8;
+      const bool dot_on = col8 < ((E + 7) & ~7);
+      float av[8];
+      *(f32x4*)av = *(const f32x4*)(att_a + col8);
+      *(f32x4*)(av + 4) = *(const f32x4*)(att_a + col8 + 4);
+#pragma unroll 2
+      for (int it = 0; it < MT * 4; ++it) {
+        const int row_l = it * 4 + (lane >> 4);
+        const long row = row0 + wave * (MT * 16) + row_l;
+        const bf16x8 v =
+            *(const bf16x8*)(lds_t + (size_t)row_l * (EP + 8) + col8);
+        float s = dot_on ? row_dot8(v, av, 0.f) : 0.f;
+        s = group16_reduce_sum(s);
+        if (row < M) {
+          *(bf16x8*)(dst_base + row * EP + col8) = v;
+          if ((lane & 15) == 0) raw_scores[row] = s;
+        }
+      }
+    } else if (EPI == 1) {
       // flush the wave's [MT*16, EP] tile as 16-B chunks (coalesced)
       const int chunks = MT * 16 * EP / 8;
       for (int c = lane; c < chunks; c += WAVE) {
@@ -559,7 +592,7 @@ void launch_bump_u64(void* p, unsigned long long delta,
   bump_u64_kernel<<<1, 1, 0, stream>>>((unsigned long long*)p, delta);
 }
 
-void launch_combiner_fwd_impl(const void* X, const void* W,
+int launch_combiner_fwd_impl(const void* X, const void* W,
                          const float* gamma,
                          const float* beta, void* out, void* z, float* mean,
                          float* rstd, long M, int KP, int EP, int E, float p,
@@ -568,6 +601,7 @@ void launch_combiner_fwd_impl(const void* X, const void* W,
                          int epilogue_mode, int gather, const int* starts,
                          const int* paths, const int* ends, const void* term,
                          const void* path, int TS, int PS,
+                         const float* att_a, float* raw_scores,
                          hipStream_t stream) {
   const int NT = EP / 16;
   const char* mt_env = getenv("C2V_COMBINER_MT");
@@ -594,38 +628,48 @@ void launch_combiner_fwd_impl(const void* X, const void* W,
     if (need <= 160 * 1024 - 2048) smem = need;
     else epi = 0;
   }
+#define CFWD_ARGS_X                                                           \
+  (const bf16*)X, (const bf16*)W, gamma, beta, (bf16*)out, (bf16*)z, mean,    \
+      rstd, M, KP, E, p, inv1mp, seed, rng_off, nullptr, nullptr, nullptr,    \
+      nullptr, nullptr, 0, 0
+#define CFWD_ARGS_G                                                           \
+  nullptr, (const bf16*)W, gamma, beta, (bf16*)out, (bf16*)z, mean, rstd, M,  \
+      KP, E, p, inv1mp, seed, rng_off, starts, paths, ends,                   \
+      (const bf16*)term, (const bf16*)path, TS, PS
+  // score-emitting flush: EP = 128 with the staged epilogue only; the
+  // caller learns from the return value whether raw_scores was written
+  if (raw_scores && NT == 8 && epi == 1 && !gather) {
+    if (occ == 4)
+      combiner_fwd_kernel<8, 1, 0, 2, 4, 1><<<grid, 256, smem, stream>>>(
+          CFWD_ARGS_X, att_a, raw_scores);
+    else if (occ == 3)
+      combiner_fwd_kernel<8, 1, 0, 2, 3, 1><<<grid, 256, smem, stream>>>(
+          CFWD_ARGS_X, att_a, raw_scores);
+    else
+      combiner_fwd_kernel<8, 1, 0, 2, 1, 1><<<grid, 256, smem, stream>>>(
+          CFWD_ARGS_X, att_a, raw_scores);
+    return 1;
+  }
 #define CASE(nt)                                                              \
   case nt:                                                                    \
     if (gather && mt == 1)                                                    \
       combiner_fwd_kernel<nt, 1, 1, 1><<<grid, 256, smem, stream>>>(          \
-          nullptr, (const bf16*)W, gamma, beta, (bf16*)out, (bf16*)z,         \
-          mean, rstd, M, KP, E, p, inv1mp, seed, rng_off, starts, paths,      \
-          ends, (const bf16*)term, (const bf16*)path, TS, PS);                \
+          CFWD_ARGS_G, nullptr, nullptr);                                     \
     else if (gather)                                                          \
       combiner_fwd_kernel<nt, 1, 1, 2><<<grid, 256, smem, stream>>>(          \
-          nullptr, (const bf16*)W, gamma, beta, (bf16*)out, (bf16*)z,         \
-          mean, rstd, M, KP, E, p, inv1mp, seed, rng_off, starts, paths,      \
-          ends, (const bf16*)term, (const bf16*)path, TS, PS);                \
+          CFWD_ARGS_G, nullptr, nullptr);                                     \
     else if (epi == 1 && occ == 4 && nt <= 10)                                \
       combiner_fwd_kernel<nt, 1, 0, 2, 4><<<grid, 256, smem, stream>>>(       \
-          (const bf16*)X, (const bf16*)W, gamma, beta, (bf16*)out, (bf16*)z,  \
-          mean, rstd, M, KP, E, p, inv1mp, seed, rng_off, nullptr, nullptr,   \
-          nullptr, nullptr, nullptr, 0, 0);                                   \
+          CFWD_ARGS_X, nullptr, nullptr);                                     \
     else if (epi == 1 && occ == 3 && nt <= 10)                                \
       combiner_fwd_kernel<nt, 1, 0, 2, 3><<<grid, 256, smem, stream>>>(       \
-          (const bf16*)X, (const bf16*)W, gamma, beta, (bf16*)out, (bf16*)z,  \
-          mean, rstd, M, KP, E, p, inv1mp, seed, rng_off, nullptr, nullptr,   \
-          nullptr, nullptr, nullptr, 0, 0);                                   \
+          CFWD_ARGS_X, nullptr, nullptr);                                     \
     else if (epi == 1)                                                        \
       combiner_fwd_kernel<nt, 1, 0><<<grid, 256, smem, stream>>>(             \
-          (const bf16*)X, (const bf16*)W, gamma, beta, (bf16*)out, (bf16*)z,  \
-          mean, rstd, M, KP, E, p, inv1mp, seed, rng_off, nullptr, nullptr,   \
-          nullptr, nullptr, nullptr, 0, 0);                                   \
+          CFWD_ARGS_X, nullptr, nullptr);                                     \
     else                                                                      \
       combiner_fwd_kernel<nt, 0, 0><<<grid, 256, smem, stream>>>(             \
-          (const bf16*)X, (const bf16*)W, gamma, beta, (bf16*)out, (bf16*)z,  \
-          mean, rstd, M, KP, E, p, inv1mp, seed, rng_off, nullptr, nullptr,   \
-          nullptr, nullptr, nullptr, 0, 0);                                   \
+          CFWD_ARGS_X, nullptr, nullptr);                                     \
     break;
   switch (NT) {
     CASE(2) CASE(4) CASE(6) CASE(8) CASE(10)
@@ -633,7 +677,27 @@ void launch_combiner_fwd_impl(const void* X, const void* W,
     default:
       printf("combiner_fwd: unsupported EP=%d\n", EP);
   }
+  return 0;
+#undef CFWD_ARGS_X
+#undef CFWD_ARGS_G
 #undef CASE
+}
+
+// combiner_fwd that also emits raw_scores[M] = out . att_a (see SCORES);
+// returns 1 when it did, 0 when the shape took a kernel without the score
+// flush (raw_scores is then untouched)
+int launch_combiner_fwd_scores(const void* X, const void* W,
+                               const float* gamma, const float* beta,
+                               void* out, void* z, float* mean, float* rstd,
+                               long M, int KP, int EP, int E, float p,
+                               unsigned long long seed,
+                               const unsigned long long* rng_off,
+                               int epilogue_mode, const float* att_a,
+                               float* raw_scores, hipStream_t stream) {
+  return launch_combiner_fwd_impl(X, W, gamma, beta, out, z, mean, rstd, M,
+                                  KP, EP, E, p, seed, rng_off, epilogue_mode,
+                                  0, nullptr, nullptr, nullptr, nullptr,
+                                  nullptr, 0, 0, att_a, raw_scores, stream);
 }
 
 void launch_combiner_fwd(const void* X, const void* W, const float* gamma,
@@ -644,7 +708,8 @@ void launch_combiner_fwd(const void* X, const void* W, const float* gamma,
                          int epilogue_mode, hipStream_t stream) {
   launch_combiner_fwd_impl(X, W, gamma, beta, out, z, mean, rstd, M, KP, EP,
                            E, p, seed, rng_off, epilogue_mode, 0, nullptr,
-                           nullptr, nullptr, nullptr, nullptr, 0, 0, stream);
+                           nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr,
+                           nullptr, stream);
 }
 
 void launch_gather_combiner_fwd(const int* starts, const int* paths,
@@ -659,7 +724,7 @@ void launch_gather_combiner_fwd(const int* starts, const int* paths,
                                 hipStream_t stream) {
   launch_combiner_fwd_impl(nullptr, W, gamma, beta, out, z, mean, rstd, M,
                            KP, EP, E, p, seed, rng_off, 1, 1, starts, paths,
-                           ends, term, path, TS, PS, stream);
+                           ends, term, path, TS, PS, nullptr, nullptr, stream);
 }
 
 void launch_combiner_bwd(const void* dout, const void* z, const void* out,

@@ -76,6 +76,34 @@ __device__ __forceinline__ float group16_reduce_sum(float x) {
   return x;
 }
 
+// One lane's share of a ccv-row dot product: s + sum_j v[j]*vec[j], j in
+// order.  Written out with contraction off — each product is rounded, then
+// added — which is what attention_fwd_kernel's phase 1 has always compiled
+// to (packed multiplies feeding a chain of adds, no FMA).  The attention
+// kernels and the combiner's score epilogue all go through it, so a score
+// has the same bits wherever it is computed.
+__device__ __forceinline__ float row_dot8(bf16x8 v, const float* vec,
+                                          float s) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float t = bf2f(v[j]) * vec[j];
+    s = s + t;
+  }
+  return s;
+}
+
+// per-16-lane-group dot of a ccv row against a vector
+// (each lane covers cols (l&15)*8 + j + 128*i)
+__device__ __forceinline__ float group_row_dot(const bf16* row,
+                                               const float* vec, int EP,
+                                               int lane16) {
+  float s = 0.f;
+  for (int e0 = lane16 * 8; e0 < EP; e0 += 128)
+    s = row_dot8(*(const bf16x8*)(row + e0), vec + e0, s);
+  return s;
+}
+
 // fp32 atomic add using the native global_atomic_add_f32 (no CAS loop).
 __device__ __forceinline__ void atomic_add_f32(float* p, float v) {
   unsafeAtomicAdd(p, v);

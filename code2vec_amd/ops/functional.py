@@ -73,6 +73,17 @@ _SLAB_SUM2 = os.environ.get("C2V_SLAB_SUM2", "1") == "1"  # dgamma+dbeta
 # launch fewer, but its step-time gain could not be told from the
 # run-to-run spread (PERF.md, "Backward fusions"), so it is opt-in.
 _LOSS_REDUCE = os.environ.get("C2V_LOSS_REDUCE", "0") == "1"
+# streaming attention pool inside CombinerAttentionPool (EP = 128, C <= 200):
+# the forward takes its raw scores from combiner_fwd's flush and reads the
+# combiner output once, from registers (attention_fwd_scores); the compact
+# backward holds a method's rows in registers (attention_bwd_compact_reg).
+# Same bits as the tiled kernels.  C2V_ATTN_STREAM=0 reverts both halves,
+# C2V_ATTN_STREAM_FWD=0 / C2V_ATTN_STREAM_BWD=0 one of them.
+_ATTN_STREAM = os.environ.get("C2V_ATTN_STREAM", "1") == "1"
+_ATTN_STREAM_FWD = (_ATTN_STREAM
+                    and os.environ.get("C2V_ATTN_STREAM_FWD", "1") == "1")
+_ATTN_STREAM_BWD = (_ATTN_STREAM
+                    and os.environ.get("C2V_ATTN_STREAM_BWD", "1") == "1")
 _NONE_T = torch.Tensor()  # "not provided" sentinel for optional kernel args
 
 # Owner-buffer gradient flow for the embedding tables (parallel/ddp.py):
@@ -856,7 +867,12 @@ class CombinerAttentionPool(torch.autograd.Function):
     bits of the CombinerLNTanh -> AttentionPool -> .to(bf16) chain.  The
     bf16 gradient of the bf16 cv output is read by the kernels directly;
     a gradient on the f32 cv output, if there is one as well, is added
-    first."""
+    first.
+
+    At C <= 200 both attention kernels are the streaming forms (see
+    _ATTN_STREAM above): combiner_fwd's flush emits the raw scores, the
+    forward and the compact backward keep a method's rows in registers.
+    Longer bags, or a switch at 0, take the tiled kernels; same bits."""
 
     @staticmethod
     def forward(ctx, x, w, gamma, beta, a, starts, E: int, p: float,
@@ -874,13 +890,27 @@ class CombinerAttentionPool(torch.autograd.Function):
         p_eff = float(p) if training else 0.0
         seed, off_t = (_philox_state(dev) if p_eff > 0.0
                        else (0, _philox_state(dev)[1]))
-        ext().combiner_fwd(x, w, gamma, beta, out, z, mean, rstd, E, p_eff,
-                           seed, off_t, _FWD_EPI)
         cv = torch.empty(B, EP, dtype=torch.float32, device=dev)
         cvb = torch.empty(B, EP, dtype=torch.bfloat16, device=dev)
         attn = torch.empty(B, C, dtype=torch.float32, device=dev)
-        ext().attention_fwd_cvb(out.view(B, C, EP), a, starts, cv, cvb, attn,
-                                E)
+        stream_ok = ext().attention_stream_ok(C, EP)
+        have_scores = False
+        if _ATTN_STREAM_FWD and stream_ok and _FWD_EPI == 1:
+            raw = torch.empty(M, dtype=torch.float32, device=dev)
+            # False (raw untouched) if the combiner took a kernel without
+            # the score flush; a host-side decision, no sync
+            have_scores = ext().combiner_fwd_scores(
+                x, w, gamma, beta, a, out, z, mean, rstd, raw, E, p_eff,
+                seed, off_t, _FWD_EPI)
+        else:
+            ext().combiner_fwd(x, w, gamma, beta, out, z, mean, rstd, E,
+                               p_eff, seed, off_t, _FWD_EPI)
+        if have_scores:
+            ext().attention_fwd_scores(out.view(B, C, EP), raw, starts, cv,
+                                       cvb, attn, E)
+        else:
+            ext().attention_fwd_cvb(out.view(B, C, EP), a, starts, cv, cvb,
+                                    attn, E)
         ctx.save_for_backward(x, w, gamma, beta, a, starts, z, mean, rstd,
                               out, attn)
         ctx.meta = (E, p_eff)
@@ -908,8 +938,13 @@ class CombinerAttentionPool(torch.autograd.Function):
         da_p = torch.empty(B, EP, dtype=torch.float32, device=dev)
         has_dattn = dattn is not None
         dattn = dattn.contiguous() if has_dattn else _NONE_T
-        ext().attention_bwd_compact(dcv, dattn, out.view(B, C, EP), a,
-                                    starts, attn, ds, da_p, E, has_dattn)
+        if _ATTN_STREAM_BWD and ext().attention_stream_ok(C, EP):
+            ext().attention_bwd_compact_reg(dcv, dattn, out.view(B, C, EP),
+                                            starts, attn, ds, da_p, E,
+                                            has_dattn)
+        else:
+            ext().attention_bwd_compact(dcv, dattn, out.view(B, C, EP), a,
+                                        starts, attn, ds, da_p, E, has_dattn)
         da = _slab_sum(da_p)
         dz = torch.empty(M, EP, dtype=torch.bfloat16, device=dev)
         nblocks = min((M + 4 - 1) // 4, 1024)

@@ -8,7 +8,9 @@ env vars read by ops/functional.py.  Usage (on a GPU box):
 (scatter + cast_clear + adam_bf16 vs the row-gathering table Adam) and
 ``bwd_fusions`` (one-launch reductions, compact attention backward and
 recomputing combiner backward vs what they replace) and ``group_tables``
-(both tables' counting sort: per-table chains vs the one merged chain) are
+(both tables' counting sort: per-table chains vs the one merged chain) and
+``attn_stream`` (streaming attention forward/backward and the combiner's
+score-emitting flush vs the tiled kernels) are
 not in the default set; asked for alone they skip building the model-shaped
 operands.
 """
@@ -281,6 +283,76 @@ def bench_bwd_fusions(dev, results, rounds=5):
         results[f"{k} min"] = vals[0]
 
 
+def bench_attn_stream(dev, results, rounds=5):
+    """The streaming attention pool against the tiled kernels on the SAME
+    buffers, alternating within each round (median / min), at the top11
+    shape B=1024, C=200, KP=320 with 30% of the contexts masked:
+      attention forward: tiled (scores + pool from the LDS tile) vs
+        attention_fwd_scores (scores given, rows prefetched to registers)
+      compact attention backward: tiled vs rows-in-registers
+      combiner_fwd without and with the score-emitting flush."""
+    from code2vec_amd.ops import ext
+
+    g = torch.Generator(device=dev).manual_seed(0)
+    B, C, E, EP, KP = 1024, 200, 100, 128, 320
+    M = B * C
+    x = torch.randn(M, KP, generator=g, device=dev).to(torch.bfloat16)
+    w = torch.zeros(EP, KP, device=dev)
+    w[:E] = torch.randn(E, KP, generator=g, device=dev) * (0.4 / KP ** 0.5)
+    w = w.to(torch.bfloat16)
+    gamma = torch.zeros(EP, device=dev)
+    gamma[:E] = torch.rand(E, generator=g, device=dev) + 0.5
+    beta = torch.zeros(EP, device=dev)
+    a = torch.zeros(EP, device=dev)
+    a[:E] = torch.randn(E, generator=g, device=dev) * 0.2
+    starts = torch.randint(1, 1000, (B, C), generator=g, device=dev,
+                           dtype=torch.int32)
+    starts[torch.rand(B, C, generator=g, device=dev) < 0.3] = 0
+    out = torch.empty(M, EP, dtype=torch.bfloat16, device=dev)
+    z = torch.empty_like(out)
+    mean = torch.empty(M, device=dev)
+    rstd = torch.empty(M, device=dev)
+    raw = torch.empty(M, device=dev)
+    Fn.reseed_dropout_rng(1234)
+    seed, off_t = Fn._philox_state(dev)
+    cv = torch.empty(B, EP, device=dev)
+    cvb = torch.empty(B, EP, dtype=torch.bfloat16, device=dev)
+    attn = torch.empty(B, C, device=dev)
+    assert ext().combiner_fwd_scores(x, w, gamma, beta, a, out, z, mean,
+                                     rstd, raw, E, 0.25, seed, off_t, 1)
+    ccv = out.view(B, C, EP)
+    ext().attention_fwd_cvb(ccv, a, starts, cv, cvb, attn, E)
+    dcvb = (torch.randn(B, EP, generator=g, device=dev) * 0.1).to(
+        torch.bfloat16)
+    ds = torch.empty(M, device=dev)
+    da_p = torch.empty(B, EP, device=dev)
+    none = torch.empty(0, device=dev)
+
+    cases = {
+        "attention_fwd tiled": lambda: ext().attention_fwd_cvb(
+            ccv, a, starts, cv, cvb, attn, E),
+        "attention_fwd_scores": lambda: ext().attention_fwd_scores(
+            ccv, raw, starts, cv, cvb, attn, E),
+        "attention_bwd compact tiled": lambda: ext().attention_bwd_compact(
+            dcvb, none, ccv, a, starts, attn, ds, da_p, E, False),
+        "attention_bwd compact reg": lambda: ext().attention_bwd_compact_reg(
+            dcvb, none, ccv, starts, attn, ds, da_p, E, False),
+        "combiner_fwd": lambda: ext().combiner_fwd(
+            x, w, gamma, beta, out, z, mean, rstd, E, 0.25, seed, off_t, 1),
+        "combiner_fwd + scores": lambda: ext().combiner_fwd_scores(
+            x, w, gamma, beta, a, out, z, mean, rstd, raw, E, 0.25, seed,
+            off_t, 1),
+    }
+    t = {k: [] for k in cases}
+    for _ in range(rounds):
+        for k, fn in cases.items():
+            t[k].append(timeit(fn, iters=20))
+    for k, vals in t.items():
+        vals.sort()
+        results[f"{k} med"] = vals[rounds // 2]
+        results[f"{k} min"] = vals[0]
+
+
 def main():
     if "--help" in sys.argv or "-h" in sys.argv:
         print(__doc__.strip())
@@ -290,11 +362,13 @@ def main():
         return
     dev = torch.device("cuda:0")
     if sys.argv[1:] in (["row_topk"], ["table_adam"], ["bwd_fusions"],
-                        ["group_tables"]):
+                        ["group_tables"], ["attn_stream"]):
         # needs none of the model-shaped operands built below
         results = {}
         if sys.argv[1] == "row_topk":
             bench_row_topk(dev, results)
+        elif sys.argv[1] == "attn_stream":
+            bench_attn_stream(dev, results)
         elif sys.argv[1] == "bwd_fusions":
             bench_bwd_fusions(dev, results)
         elif sys.argv[1] == "group_tables":
