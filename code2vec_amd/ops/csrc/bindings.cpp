@@ -118,6 +118,10 @@ void launch_row_max_argmax(const void*, float*, long*, long, long,
 int row_topk_chunk();
 void launch_row_topk(const void*, int, long, long, int, void*, float*, float*,
                      float*, long*, float*, hipStream_t);
+int sim_topk_query_tile();
+int sim_topk_row_tile();
+void launch_sim_topk(const void*, const void*, const long*, long, long, int,
+                     int, int, void*, float*, long*, hipStream_t);
 void launch_head_bwd_prep(const long*, const float*, const float*,
                           const float*, const float*, float*, long,
                           hipStream_t);
@@ -991,6 +995,62 @@ void row_topk(torch::Tensor x, int64_t k, int64_t chunk, torch::Tensor part,
                   lse.data_ptr<float>(), cur_stream());
 }
 
+// K20: fused similarity + top-k.  q [nq, EP] bf16, db [N, EP] bf16;
+// vals f32 [nq, k], idx i64 [nq, k] in K19's order (descending score, ties
+// to the smallest index row).  exclude (i64 [nq], or an empty tensor for
+// none) names one index row per query that is never returned, -1 = none.
+// part (i64 [nq, nsplit, 16]) is only touched when nsplit > 1.
+// query_tile/row_tile are the caller's idea of the kernel's tiles.
+void sim_topk(torch::Tensor q, torch::Tensor db, torch::Tensor exclude,
+              int64_t k, int64_t nsplit, int64_t query_tile, int64_t row_tile,
+              torch::Tensor part, torch::Tensor vals, torch::Tensor idx) {
+  CHK_CUDA(q); CHK_CONTIG(q); CHK_DT(q, torch::kBFloat16);
+  CHK_CUDA(db); CHK_CONTIG(db); CHK_DT(db, torch::kBFloat16);
+  TORCH_CHECK(q.dim() == 2 && db.dim() == 2,
+              "sim_topk: q must be [nq, EP] and db [N, EP]");
+  const long nq = q.size(0), EP = q.size(1), N = db.size(0);
+  TORCH_CHECK(db.size(1) == EP, "sim_topk: q has EP = ", EP, ", db has ",
+              db.size(1));
+  TORCH_CHECK(EP % 32 == 0 && EP >= 32 && EP <= 512,
+              "sim_topk: EP must be a multiple of 32 in 32..512, got ", EP);
+  TORCH_CHECK(query_tile == sim_topk_query_tile() &&
+              row_tile == sim_topk_row_tile(),
+              "sim_topk: tiles ", query_tile, "x", row_tile,
+              " != compiled ", sim_topk_query_tile(), "x",
+              sim_topk_row_tile());
+  TORCH_CHECK(k >= 1 && k <= 16, "sim_topk: k must be in 1..16, got ", k);
+  TORCH_CHECK(N < (1L << 31) && nq < (1L << 31),
+              "sim_topk: N and nq must be < 2^31");
+  TORCH_CHECK(k <= N, "sim_topk: k = ", k, " exceeds the index's ", N,
+              " rows");
+  const long* ex = nullptr;
+  if (exclude.numel() > 0) {
+    CHK_CUDA(exclude); CHK_CONTIG(exclude); CHK_DT(exclude, torch::kInt64);
+    TORCH_CHECK(exclude.dim() == 1 && exclude.size(0) == nq,
+                "sim_topk: exclude must be [nq]");
+    TORCH_CHECK(k <= N - 1, "sim_topk: with exclude, k = ", k,
+                " must be below the index's ", N, " rows");
+    ex = exclude.data_ptr<long>();
+  }
+  const long nqt = (nq + query_tile - 1) / query_tile;
+  TORCH_CHECK(nsplit >= 1 && nsplit * std::max(nqt, 1L) < (1L << 31),
+              "sim_topk: nsplit = ", nsplit, " gives an invalid grid");
+  CHK_CUDA(vals); CHK_CONTIG(vals); CHK_DT(vals, torch::kFloat32);
+  CHK_CUDA(idx); CHK_CONTIG(idx); CHK_DT(idx, torch::kInt64);
+  TORCH_CHECK(vals.numel() == nq * k && idx.numel() == nq * k,
+              "sim_topk: output shapes");
+  void* pp = nullptr;
+  if (nsplit > 1) {
+    CHK_CUDA(part); CHK_CONTIG(part); CHK_DT(part, torch::kInt64);
+    TORCH_CHECK(part.numel() >= nq * nsplit * 16,
+                "sim_topk: partials too small");
+    pp = part.data_ptr();
+  }
+  launch_sim_topk(q.data_ptr(), db.data_ptr(), ex, nq, N, (int)EP, (int)k,
+                  (int)nsplit, pp, vals.data_ptr<float>(),
+                  idx.data_ptr<long>(), cur_stream());
+}
+
 void transpose_w(torch::Tensor w, torch::Tensor wt) {
   CHK_CUDA(w); CHK_CONTIG(w); CHK_DT(w, torch::kBFloat16);
   CHK_CONTIG(wt); CHK_DT(wt, torch::kBFloat16);
@@ -1447,6 +1507,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("swizzle_cv", &swizzle_cv);
   m.def("row_max_argmax", &row_max_argmax);
   m.def("row_topk", &row_topk);
+  m.def("sim_topk", &sim_topk);
   m.def("inv_rownorm", &inv_rownorm);
   m.def("rowscale", &rowscale);
   m.def("angular_fwd", &angular_fwd);

@@ -1389,6 +1389,127 @@ def topk_probs(vals: torch.Tensor, lse: torch.Tensor) -> torch.Tensor:
     return torch.exp(vals - lse[:, None])
 
 
+# K20 tiles: queries per block (the index is streamed once per query tile)
+# and index rows per MFMA tile (slice boundaries fall on multiples of it).
+# The extension checks both against the compiled values.
+SIM_QUERY_TILE = 16
+SIM_ROW_TILE = 16
+# stage-1 blocks the default nsplit aims for (a few per CU of a 256-CU
+# device; results do not depend on nsplit, so this is a constant)
+_SIM_TARGET_BLOCKS = 1024
+# tiles a slice should at least hold: every block fills its lists from
+# empty, which threshold-first selection only repays on a long stream
+# (PERF.md, "Similarity search": the nsplit sweep)
+_SIM_MIN_SLICE_TILES = 128
+# C2V_SIM_FUSED=0 routes sim_topk to sim_topk_composed (A/B baseline)
+_SIM_FUSED = os.environ.get("C2V_SIM_FUSED", "1") == "1"
+_SIM_COMPOSED_SCORE_BYTES = 1 << 30
+
+
+def sim_topk_default_nsplit(nq: int, N: int) -> int:
+    """Index slices K20 uses when the caller does not force a number."""
+    nqt = max(1, -(-nq // SIM_QUERY_TILE))
+    ntile = -(-N // SIM_ROW_TILE)
+    return max(1, min(-(-_SIM_TARGET_BLOCKS // nqt),
+                      ntile // _SIM_MIN_SLICE_TILES))
+
+
+def sim_topk_slice_rows(N: int, nsplit: int) -> int:
+    """Index rows per slice for a given nsplit (slice s owns rows
+    [s * rows, (s + 1) * rows)); exposed so tests can plant values on
+    slice boundaries."""
+    ntile = -(-N // SIM_ROW_TILE)
+    return -(-ntile // nsplit) * SIM_ROW_TILE
+
+
+def _sim_topk_check_device(q, db):
+    if q.dtype != torch.bfloat16 or db.dtype != torch.bfloat16:
+        raise ValueError(
+            f"sim_topk: device inputs must be bf16, got {q.dtype} and "
+            f"{db.dtype}")
+    if q.device != db.device:
+        raise ValueError("sim_topk: q and db must be on the same device")
+    if not (q.is_contiguous() and db.is_contiguous()):
+        raise ValueError("sim_topk: device inputs must be contiguous")
+
+
+def sim_topk(q: torch.Tensor, db: torch.Tensor, k: int, exclude=None,
+             nsplit: Optional[int] = None):
+    """K20: per query row of q [nq, EP], the k (1..16) rows of db [N, EP]
+    with the largest dot product, without materializing the [nq, N] score
+    matrix.  Returns (vals f32 [nq, k], idx i64 [nq, k]) in row_topk's
+    total order (descending score, ties to the smallest index row).
+    ``exclude`` [nq] i64: one index row per query that is never returned
+    (-1: none).  Device bf16 input runs the HIP kernel (no host sync;
+    capturable); CPU tensors take ops/reference.py::sim_topk.  ``nsplit``
+    forces the number of index slices (results do not depend on it)."""
+    from . import reference as R
+
+    k = int(k)
+    R.check_sim_topk_args(q, db, k, exclude)
+    if not (q.is_cuda or db.is_cuda):
+        return R.sim_topk(q, db, k, exclude)
+    _sim_topk_check_device(q, db)
+    if not _SIM_FUSED:
+        return sim_topk_composed(q, db, k, exclude)
+    nq, N = q.shape[0], db.shape[0]
+    dev = q.device
+    if exclude is not None:
+        if exclude.device != dev or not exclude.is_contiguous():
+            raise ValueError(
+                "sim_topk: exclude must be contiguous on the inputs' device")
+    if nsplit is None:
+        nsplit = sim_topk_default_nsplit(nq, N)
+    nsplit = int(nsplit)
+    if nsplit < 1:
+        raise ValueError(f"sim_topk: nsplit must be >= 1, got {nsplit}")
+    vals = torch.empty(nq, k, dtype=torch.float32, device=dev)
+    idx = torch.empty(nq, k, dtype=torch.int64, device=dev)
+    if nq == 0:
+        return vals, idx
+    part = (torch.empty(nq, nsplit, 16, dtype=torch.int64, device=dev)
+            if nsplit > 1 else _NONE_T)
+    ext().sim_topk(q, db, exclude if exclude is not None else _NONE_T, k,
+                   nsplit, SIM_QUERY_TILE, SIM_ROW_TILE, part, vals, idx)
+    return vals, idx
+
+
+def sim_topk_composed(q: torch.Tensor, db: torch.Tensor, k: int,
+                      exclude=None):
+    """sim_topk's contract through existing parts: an fp32 matmul per
+    query chunk (chunks sized so the scores stay under about 1 GiB), then
+    row_topk (K19).  The A/B baseline of the fused kernel; scores differ
+    from K20's only by fp32 summation order."""
+    from . import reference as R
+
+    k = int(k)
+    R.check_sim_topk_args(q, db, k, exclude)
+    if q.is_cuda or db.is_cuda:
+        _sim_topk_check_device(q, db)
+    nq, N = q.shape[0], db.shape[0]
+    dev = q.device
+    vals = torch.empty(nq, k, dtype=torch.float32, device=dev)
+    idx = torch.empty(nq, k, dtype=torch.int64, device=dev)
+    dbt = db.float().t()
+    step = max(1, _SIM_COMPOSED_SCORE_BYTES // (4 * N))
+    for a in range(0, nq, step):
+        b = min(nq, a + step)
+        S = q[a:b].float() @ dbt
+        if exclude is not None:
+            ex = exclude[a:b].to(dev)
+            # no host sync: excluded entries via a one-column scatter whose
+            # "none" rows (-1) rewrite column 0 with its own value
+            col = ex.clamp(0, N - 1).view(-1, 1)
+            cur = S.gather(1, col)
+            hit = ((ex >= 0) & (ex < N)).view(-1, 1)
+            S.scatter_(1, col, torch.where(
+                hit, torch.full_like(cur, float("-inf")), cur))
+        v, i, _ = row_topk(S, k)
+        vals[a:b] = v
+        idx[a:b] = i
+    return vals, idx
+
+
 def adam_step(
     param: torch.Tensor,
     grad: torch.Tensor,

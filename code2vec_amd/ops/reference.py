@@ -119,6 +119,55 @@ def row_topk(x, k: int):
             torch.logsumexp(xf, dim=1))
 
 
+SIM_TOPK_MAX_EP = 512
+
+
+def check_sim_topk_args(q, db, k: int, exclude=None) -> None:
+    """Argument contract shared by the oracle and the HIP op (K20)."""
+    if q.dim() != 2 or db.dim() != 2:
+        raise ValueError(
+            f"sim_topk: q must be [nq, EP] and db [N, EP], got "
+            f"{tuple(q.shape)} and {tuple(db.shape)}")
+    EP, N = q.shape[1], db.shape[0]
+    if db.shape[1] != EP:
+        raise ValueError(
+            f"sim_topk: q has EP = {EP}, db has EP = {db.shape[1]}")
+    if EP % 32 != 0 or not 32 <= EP <= SIM_TOPK_MAX_EP:
+        raise ValueError(
+            f"sim_topk: EP must be a multiple of 32 in "
+            f"32..{SIM_TOPK_MAX_EP}, got {EP}")
+    if not 1 <= k <= ROW_TOPK_MAX_K:
+        raise ValueError(
+            f"sim_topk: k must be in 1..{ROW_TOPK_MAX_K}, got {k}")
+    if N >= 1 << 31:
+        raise ValueError("sim_topk: N must be < 2^31")
+    if k > N:
+        raise ValueError(f"sim_topk: k = {k} exceeds the index's {N} rows")
+    if exclude is not None:
+        if exclude.dim() != 1 or exclude.shape[0] != q.shape[0] \
+                or exclude.dtype != torch.int64:
+            raise ValueError("sim_topk: exclude must be int64 [nq]")
+        if k > N - 1:
+            raise ValueError(
+                f"sim_topk: with exclude, k = {k} must be below the "
+                f"index's {N} rows")
+
+
+def sim_topk(q, db, k: int, exclude=None):
+    """K20: the k index rows of ``db`` with the largest dot product per
+    query row of ``q``, in row_topk's total order (descending score, ties
+    to the smallest index row).  ``exclude`` [nq] i64 names one index row
+    per query that is never returned (-1: none).  Returns (vals f32
+    [nq, k], idx i64 [nq, k])."""
+    check_sim_topk_args(q, db, k, exclude)
+    S = q.float() @ db.float().t()
+    if exclude is not None:
+        ex = exclude.to(S.device)
+        rows = torch.nonzero((ex >= 0) & (ex < db.shape[0])).flatten()
+        S[rows, ex[rows]] = float("-inf")
+    return row_topk(S, k)[:2]
+
+
 def logsoftmax_nll(logits, label, weight):
     """K12: log_softmax + weighted NLL (reference main.py:251-264 with the
     criterion built at main.py:129-130).
