@@ -137,8 +137,8 @@ void launch_norm_project(const void*, const void*, const float*, void*,
 void launch_head_bwd_dw(const void*, const void*, const float*, void*,
                         float*, long, long, hipStream_t);
 void launch_head_bwd_dcv_rc(const void*, const void*, const void*,
-                            const float*, float*, long, long, int,
-                            hipStream_t);
+                            const float*, const float*, float*, long, long,
+                            int, hipStream_t);
 void launch_head_bwd_dcv(const void*, const void*, const float*, float*,
                          long, long, int, hipStream_t);
 void launch_head_fwd(const void*, const void*, const float*, void*, float*,
@@ -853,15 +853,19 @@ void head_bwd_dcv(torch::Tensor logits, torch::Tensor wimg,
 }
 
 // Streaming dcv: logits never read — recomputed per wave from the
-// swizzle_a fragment images of cv ([B,128]) and W ([L,128]).
+// swizzle_a fragment images of cv ([B,128]) and W ([L,128]) plus the f32
+// bias [L].
 void head_bwd_dcv_rc(torch::Tensor cvimg_a, torch::Tensor wimg_a,
-                     torch::Tensor wimg, torch::Tensor coef_lse,
-                     torch::Tensor partials, long B, long L, long chunk) {
+                     torch::Tensor wimg, torch::Tensor bias,
+                     torch::Tensor coef_lse, torch::Tensor partials, long B,
+                     long L, long chunk) {
   CHK_CUDA(wimg); CHK_CONTIG(wimg); CHK_DT(wimg, torch::kBFloat16);
   CHK_CONTIG(cvimg_a); CHK_DT(cvimg_a, torch::kBFloat16);
   CHK_CONTIG(wimg_a); CHK_DT(wimg_a, torch::kBFloat16);
+  CHK_CUDA(bias); CHK_CONTIG(bias); CHK_DT(bias, torch::kFloat32);
   CHK_CONTIG(coef_lse); CHK_DT(coef_lse, torch::kFloat32);
   CHK_DT(partials, torch::kFloat32); CHK_CONTIG(partials);
+  TORCH_CHECK(bias.numel() == L, "bias must be [L]");
   TORCH_CHECK(wimg.numel() == (L + 127) / 128 * 4 * 4096,
               "wimg must be [ceil(L/128)*4, 8, 64, 8]");
   TORCH_CHECK(cvimg_a.numel() >= (B + 127) / 128 * 8 * 2048,
@@ -874,7 +878,8 @@ void head_bwd_dcv_rc(torch::Tensor cvimg_a, torch::Tensor wimg_a,
   TORCH_CHECK(partials.numel() == (L + chunk - 1) / chunk * B * 128,
               "head_bwd_dcv_rc partials shape");
   launch_head_bwd_dcv_rc(cvimg_a.data_ptr(), wimg_a.data_ptr(),
-                         wimg.data_ptr(), coef_lse.data_ptr<float>(),
+                         wimg.data_ptr(), bias.data_ptr<float>(),
+                         coef_lse.data_ptr<float>(),
                          partials.data_ptr<float>(), B, L, (int)chunk,
                          cur_stream());
 }

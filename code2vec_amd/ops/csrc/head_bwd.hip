@@ -519,13 +519,19 @@ __global__ __launch_bounds__(512) void head_bwd_dcv_kernel(
 // duplicating the forward GEMM's FLOPs (~68 GFLOP, ~3% of one MFMA-second)
 // — the trade the MI355X's 2.5-PFLOP/s : 5.5-TB/s ratio is built for.
 //
-// The recomputed logits are the f32 MFMA accumulators — one bf16 rounding
-// CLOSER to the forward's online-softmax stats (which were computed from
-// the same f32 tiles) than the stored-logits kernel above.
+// The recomputed logits are the f32 MFMA accumulators plus the f32 bias,
+// as in the forward's epilogue BEFORE its bf16 rounding.  The forward's
+// online-softmax stats (and so lse) are taken from the bf16-ROUNDED value
+// (head_fwd.hip, "stats from the bf16-rounded value"), so the exponent here,
+// unrounded logit - lse, is one rounding FURTHER from lse than in the
+// stored-logits kernel above: off by the logit's rounding error, up to
+// 2^-9 |logit| (0.06 at a logit of 32).  G then differs from the
+// stored-logits kernel's by that factor and sum_l p_l is not exactly 1.
 __global__ __launch_bounds__(512) void head_bwd_dcv_rc_kernel(
     const bf16* __restrict__ cvimg_a, const bf16* __restrict__ wimg_a,
-    const bf16* __restrict__ wimg, const float* __restrict__ coef_lse,
-    float* __restrict__ partials, long B, long L, int chunk, int GYB) {
+    const bf16* __restrict__ wimg, const float* __restrict__ bias,
+    const float* __restrict__ coef_lse, float* __restrict__ partials, long B,
+    long L, int chunk, int GYB) {
   const int lane = threadIdx.x & (WAVE - 1);
   const int wave = threadIdx.x / WAVE;
   const int total = gridDim.x;
@@ -592,6 +598,7 @@ __global__ __launch_bounds__(512) void head_bwd_dcv_rc_kernel(
       c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
           acv3, *(const bf16x8*)(wp + 1536), c, 0, 0, 0);
       const long lab = l0s + nt2 * 16 + (lane & 15);
+      const float bl = lab < L ? bias[lab] : 0.f;
       const int lab32 = (nt2 & 1) * 16 + (lane & 15);
       const int ebase = ((lab32 >> 3) * 16) * 8 + (lab32 & 7);
       bf16* gout = gst[wave][nt2 >> 1];
@@ -599,7 +606,7 @@ __global__ __launch_bounds__(512) void head_bwd_dcv_rc_kernel(
       for (int r = 0; r < 4; ++r) {
         float g = 0.f;
         if (lab < L) {
-          g = coef4[r] * __expf(c[r] - lse4[r]);
+          g = coef4[r] * __expf(c[r] + bl - lse4[r]);
           if ((float)lab == yf4[r]) g -= coef4[r];
         }
         gout[ebase + (((lane >> 4) * 4 + r)) * 8] = f2bf(g);
@@ -691,13 +698,13 @@ void launch_head_bwd_dcv(const void* logits, const void* wimg,
 }
 
 void launch_head_bwd_dcv_rc(const void* cvimg_a, const void* wimg_a,
-                            const void* wimg, const float* coef_lse,
-                            float* partials, long B, long L, int chunk,
-                            hipStream_t stream) {
+                            const void* wimg, const float* bias,
+                            const float* coef_lse, float* partials, long B,
+                            long L, int chunk, hipStream_t stream) {
   const int GYB = (int)((B + 127) / 128);
   const int split = (int)((L + chunk - 1) / chunk);
   head_bwd_dcv_rc_kernel<<<GYB * split, 512, 0, stream>>>(
-      (const bf16*)cvimg_a, (const bf16*)wimg_a, (const bf16*)wimg,
+      (const bf16*)cvimg_a, (const bf16*)wimg_a, (const bf16*)wimg, bias,
       coef_lse, partials, B, L, chunk, GYB);
 }
 

@@ -1081,12 +1081,15 @@ class FusedLogSoftmaxNLL(torch.autograd.Function):
     """K12: full-vocab log-softmax + weighted NLL, fused fwd and bwd.
 
     logits: bf16 [B, L]; label: i64 [B]; weight: f32 [L] (1/freq weights,
-    reference main.py:129-130).  loss = sum(w_y*(lse - logit_y)) / sum(w_y).
+    reference main.py:129-130) or None for w = 1.
+    loss = sum(w_y*(lse - logit_y)) / sum(w_y).
     """
 
     @staticmethod
     def forward(ctx, logits, label, weight):
         B, L = logits.shape
+        if weight is None:  # unweighted: the kernels take w_y = 1
+            weight = _NONE_T
         lse = torch.empty(B, dtype=torch.float32, device=logits.device)
         # acc[0] = sum(w_y * nll), acc[1] = sum(w_y)
         partials = getattr(logits, "_c2v_lsm_partials", None)
@@ -1252,6 +1255,8 @@ class FusedHeadLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, cv_bf16, w, bias, label, weight):
         B, L = logits.shape
+        if weight is None:  # unweighted: the kernels take w_y = 1
+            weight = _NONE_T
         lse = torch.empty(B, dtype=torch.float32, device=logits.device)
         partials = getattr(logits, "_c2v_lsm_partials", None)
         if partials is not None:
@@ -1260,7 +1265,8 @@ class FusedHeadLoss(torch.autograd.Function):
             acc, loss = _finalize_stats(logits, pm, ps, label, weight, lse)
         else:
             acc, loss = _lsm_stats(logits, label, weight, lse)
-        ctx.save_for_backward(logits, cv_bf16, w, label, weight, lse, acc)
+        ctx.save_for_backward(logits, cv_bf16, w, label, weight, lse, acc,
+                              bias)
         # saved_tensors re-wraps the tensor object, so python attributes
         # do not survive — carry the forward's W fragment image on ctx
         ctx.wimg_a = getattr(logits, "_c2v_wimg_a", None)
@@ -1268,7 +1274,7 @@ class FusedHeadLoss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dloss):
-        logits, cv, w, label, weight, lse, acc = ctx.saved_tensors
+        logits, cv, w, label, weight, lse, acc, bias = ctx.saved_tensors
         B, L = logits.shape
         dev = w.device
         g = dloss.contiguous().float().view(1)
@@ -1302,7 +1308,7 @@ class FusedHeadLoss(torch.autograd.Function):
             # STREAMING dcv: the [B, L] logits are never read — each wave
             # recomputes its logits tile by MFMA from the swizzle_a
             # fragment images of cv and W (the W image is reused from the
-            # forward when head_fwd_img ran)
+            # forward when head_fwd_img ran) and adds the f32 bias
             cvimg_a = _scratch_bf16(
                 "head_cvimg_a", ((B + 255) // 256 * 16, 4, 64, 8), dev)
             ext().swizzle_a(cv.contiguous(), cvimg_a)
@@ -1311,8 +1317,9 @@ class FusedHeadLoss(torch.autograd.Function):
                 wimg_a = _scratch_bf16(
                     "hf_aimg", ((L + 255) // 256 * 16, 4, 64, 8), dev)
                 ext().swizzle_a(w, wimg_a)
-            ext().head_bwd_dcv_rc(cvimg_a, wimg_a, wimg, coef_lse,
-                                  partials, B, L, chunk)
+            ext().head_bwd_dcv_rc(cvimg_a, wimg_a, wimg,
+                                  bias.detach().float().contiguous(),
+                                  coef_lse, partials, B, L, chunk)
         else:
             ext().head_bwd_dcv(logits, wimg, coef_lse, partials, chunk)
         dcv = torch.empty(B, 128, dtype=torch.bfloat16, device=dev)

@@ -573,9 +573,14 @@ class TestFusedHeadLoss:
         assert relerr(dbias.float(), br.grad) < 3e-2
 
     def test_large_vocab_library_fwd_path(self, dev):
-        """L > C2V_HEAD_FWD_MAXL: forward takes the hipBLASLt path (no
-        stats partials -> full lsm fwd) and backward the 4096-label-chunk
-        split; still must match the oracle."""
+        """A large vocabulary, L = 70016.  Despite its name this test does
+        not reach the library GEMM: L is a multiple of 8 and EP = 128, so
+        the forward is head_fwd_img (the W-image kernel, the default since
+        it replaced the C2V_HEAD_FWD_MAXL gate here) with the stats
+        partials merged by lsm_finalize, and the backward splits dcv in
+        1024-label chunks (4096 starts above L = 131072).  The library
+        forward followed by lsm_partial, and the 4096-label chunk, are
+        covered in test_head_numerics_gpu.py."""
         B, L = 32, 70016
         cv, w, bias, label, weight = self._setup(dev, B, L, seed=31)
         loss, dcv, dw, dbias = self._run_fused(cv, w, bias, label, weight)

@@ -563,8 +563,8 @@ def main():
         results["swizzle_a(cv)"] = timeit(
             lambda: ext().swizzle_a(cvb, cvimg_a))
         results["head_bwd_dcv_rc"] = timeit(
-            lambda: ext().head_bwd_dcv_rc(cvimg_a, wimg_a, wimg, coef_lse,
-                                          partials, B, L, chunk))
+            lambda: ext().head_bwd_dcv_rc(cvimg_a, wimg_a, wimg, bias,
+                                          coef_lse, partials, B, L, chunk))
 
     if "row_topk" in ops:
         bench_row_topk(dev, results)
