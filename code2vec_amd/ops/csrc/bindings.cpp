@@ -100,6 +100,8 @@ void launch_lsm_nll_fwd(const void*, const long*, const float*, float*,
 void launch_lsm_nll_bwd(const void*, const long*, const float*, const float*,
                         const float*, const float*, void*, int, long,
                         hipStream_t);
+bool launch_wgrad_pipe(const void*, const void*, float*, long, int, int, int,
+                       int, hipStream_t);
 void launch_wgrad(const void*, const void*, float*, long, int, int, int,
                   hipStream_t);
 void launch_dgrad(const void*, const void*, void*, long, int, int,
@@ -136,6 +138,10 @@ void launch_norm_project(const void*, const void*, const float*, void*,
                          long, hipStream_t);
 void launch_head_bwd_dw(const void*, const void*, const float*, void*,
                         float*, long, long, hipStream_t);
+bool launch_head_bwd_dw_pipe(const void*, const void*, const float*, void*,
+                             float*, long, long, int, hipStream_t);
+void launch_head_bwd_dcv_pipe(const void*, const void*, const float*, float*,
+                              long, long, int, int, hipStream_t);
 void launch_head_bwd_dcv_rc(const void*, const void*, const void*,
                             const float*, const float*, float*, long, long,
                             int, hipStream_t);
@@ -852,6 +858,58 @@ void head_bwd_dcv(torch::Tensor logits, torch::Tensor wimg,
                       cur_stream());
 }
 
+// Pipelined head_bwd_dw (bit-identical outputs): depth = 64-row
+// sub-stages per K-loop stage, 0 = C2V_HB_DW_DEPTH or the shipped default.
+void head_bwd_dw_pipe(torch::Tensor logits, torch::Tensor cvimg,
+                      torch::Tensor coef_lse, torch::Tensor dw,
+                      torch::Tensor dbias, long depth) {
+  CHK_CUDA(logits); CHK_CONTIG(logits); CHK_DT(logits, torch::kBFloat16);
+  CHK_CONTIG(cvimg); CHK_DT(cvimg, torch::kBFloat16);
+  CHK_CONTIG(coef_lse); CHK_DT(coef_lse, torch::kFloat32);
+  CHK_CONTIG(dw); CHK_DT(dw, torch::kBFloat16);
+  CHK_CONTIG(dbias); CHK_DT(dbias, torch::kFloat32);
+  const long B = logits.size(0), L = logits.size(1);
+  TORCH_CHECK(B > 0 && L > 0, "head_bwd_dw_pipe needs B, L > 0");
+  TORCH_CHECK(cvimg.numel() == (B + 63) / 64 * 2 * 4096, "cvimg shape");
+  TORCH_CHECK(L % 8 == 0 && B % 8 == 0, "head_bwd_dw_pipe shape gates");
+  TORCH_CHECK(L < (1L << 24), "label index carried as f32 needs L < 2^24");
+  TORCH_CHECK(coef_lse.numel() == 4 * B, "coef_lse must be [B, 4]");
+  TORCH_CHECK(dw.size(0) == L && dw.size(1) == 128 && dbias.numel() == L,
+              "head_bwd_dw_pipe output shapes");
+  TORCH_CHECK(launch_head_bwd_dw_pipe(
+                  logits.data_ptr(), cvimg.data_ptr(),
+                  coef_lse.data_ptr<float>(), dw.data_ptr(),
+                  dbias.data_ptr<float>(), B, L, (int)depth, cur_stream()),
+              "head_bwd_dw_pipe: no instantiation for this depth / "
+              "C2V_HBDW_VARIANT");
+}
+
+// Pipelined head_bwd_dcv (bit-identical partials): dbuf = 1 double-buffers
+// the W image in LDS, 0 keeps one buffer, -1 = C2V_HB_DCV_DBUF or the
+// shipped default.
+void head_bwd_dcv_pipe(torch::Tensor logits, torch::Tensor wimg,
+                       torch::Tensor coef_lse, torch::Tensor partials,
+                       long chunk, long dbuf) {
+  CHK_CUDA(logits); CHK_CONTIG(logits); CHK_DT(logits, torch::kBFloat16);
+  CHK_CONTIG(wimg); CHK_DT(wimg, torch::kBFloat16);
+  CHK_CONTIG(coef_lse); CHK_DT(coef_lse, torch::kFloat32);
+  CHK_DT(partials, torch::kFloat32); CHK_CONTIG(partials);
+  const long B = logits.size(0), L = logits.size(1);
+  TORCH_CHECK(B > 0 && L > 0, "head_bwd_dcv_pipe needs B, L > 0");
+  TORCH_CHECK(wimg.numel() == (L + 127) / 128 * 4 * 4096,
+              "wimg must be [ceil(L/128)*4, 8, 64, 8]");
+  TORCH_CHECK(L % 8 == 0 && chunk > 0 && chunk % 128 == 0,
+              "head_bwd_dcv_pipe shape gates");
+  TORCH_CHECK(L < (1L << 24), "label index carried as f32 needs L < 2^24");
+  TORCH_CHECK(coef_lse.numel() == 4 * B, "coef_lse must be [B, 4]");
+  TORCH_CHECK(partials.numel() == (L + chunk - 1) / chunk * B * 128,
+              "head_bwd_dcv_pipe partials shape");
+  launch_head_bwd_dcv_pipe(logits.data_ptr(), wimg.data_ptr(),
+                           coef_lse.data_ptr<float>(),
+                           partials.data_ptr<float>(), B, L, (int)chunk,
+                           (int)dbuf, cur_stream());
+}
+
 // Streaming dcv: logits never read — recomputed per wave from the
 // swizzle_a fragment images of cv ([B,128]) and W ([L,128]) plus the f32
 // bias [L].
@@ -1157,6 +1215,25 @@ void wgrad(torch::Tensor x, torch::Tensor dz, torch::Tensor partials) {
   TORCH_CHECK(partials.size(1) == KP && partials.size(2) == EP, "partials");
   launch_wgrad(x.data_ptr(), dz.data_ptr(), partials.data_ptr<float>(), M,
                KP, EP, partials.size(0), cur_stream());
+}
+
+// Pipelined split-K wgrad (bit-identical slabs): depth = 32-row K-steps
+// per stage, 0 = C2V_WGRAD_DEPTH or the shipped default.
+void wgrad_pipe(torch::Tensor x, torch::Tensor dz, torch::Tensor partials,
+                long depth) {
+  CHK_CUDA(x); CHK_CONTIG(x); CHK_DT(x, torch::kBFloat16);
+  CHK_CONTIG(dz); CHK_DT(dz, torch::kBFloat16);
+  CHK_DT(partials, torch::kFloat32); CHK_CONTIG(partials);
+  const long M = x.size(0);
+  const int KP = x.size(1), EP = dz.size(1);
+  TORCH_CHECK(dz.size(0) == M, "wgrad_pipe: x and dz row counts differ");
+  TORCH_CHECK(partials.dim() == 3 && partials.size(1) == KP &&
+                  partials.size(2) == EP, "partials");
+  TORCH_CHECK(launch_wgrad_pipe(x.data_ptr(), dz.data_ptr(),
+                                partials.data_ptr<float>(), M, KP, EP,
+                                partials.size(0), (int)depth, cur_stream()),
+              "wgrad_pipe: no instantiation for KP=", KP, " EP=", EP,
+              " depth=", depth);
 }
 
 // bc_pow: float64 [2] DEVICE tensor = (beta1^t, beta2^t); advance it with
@@ -1497,6 +1574,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("logsoftmax_nll_fwd", &logsoftmax_nll_fwd);
   m.def("logsoftmax_nll_bwd", &logsoftmax_nll_bwd);
   m.def("wgrad", &wgrad);
+  m.def("wgrad_pipe", &wgrad_pipe);
   m.def("colsum_bf16", &colsum_bf16);
   m.def("head_fwd", &head_fwd);
   m.def("head_fwd_img", &head_fwd_img);
@@ -1521,6 +1599,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("head_bwd_dw", &head_bwd_dw);
   m.def("head_bwd_dcv", &head_bwd_dcv);
   m.def("head_bwd_dcv_rc", &head_bwd_dcv_rc);
+  m.def("head_bwd_dw_pipe", &head_bwd_dw_pipe);
+  m.def("head_bwd_dcv_pipe", &head_bwd_dcv_pipe);
   m.def("transpose_w", &transpose_w);
   m.def("dgrad2", &dgrad2);
   m.def("slab_sum_bf16", &slab_sum_bf16);

@@ -32,9 +32,9 @@
 // Kernel 2 (batch-major): dcv[B, EP] = G @ W — head_dgrad.hip's proven
 //   split-K structure with the A fragment recomputed from contiguous
 //   logits row chunks instead of read from dlogits.  The label chunk per
-//   block is a runtime parameter: 512 at L <= 64k (59 slabs at top11),
-//   4096 at java-large scale so the fp32 partial-slab traffic stays ~33 MB
-//   instead of 268 MB.
+//   block is a runtime parameter: 1024 up to L = 131072 (71 slabs at
+//   top11), 4096 above (java-large) so the fp32 partial-slab traffic stays
+//   ~33 MB instead of 268 MB.
 
 #include <cstdlib>
 
@@ -43,6 +43,8 @@
 #define HB_LB 64    // labels per dW block
 #define HB_ROWS 64  // batch rows staged per K-iteration
 #define HB_NSTR (64 * 8 + 8)  // padded A-image stride (wgrad recipe)
+#define HB_DW_DEPTH 2   // shipped sub-stages per stage of head_bwd_dw_pipe
+#define HB_DCV_DBUF 1   // W-image buffering of head_bwd_dcv_pipe_kernel
 
 // coef_lse[b] = (coef_b, lse_b, (float)y_b, 0)
 __global__ __launch_bounds__(256) void head_bwd_prep_kernel(
@@ -231,6 +233,243 @@ __global__ __launch_bounds__(512, MINW) void head_bwd_dw_kernel(
 #pragma unroll
     for (int q = 0; q < 8; ++q) s += red2[q][threadIdx.x];
     dbias[l0 + threadIdx.x] = s;
+  }
+}
+
+// three live floats of a coef_lse row: a 12-byte load leaves no dead
+// destination register for the allocator to reuse while the load is in
+// flight (reuse forces a full vmcnt drain)
+struct __attribute__((aligned(16))) hb_meta3 {
+  float coef, lse, yf;
+};
+
+// PIPELINED head_bwd_dw: same arithmetic, same G image, same dbias
+// ownership and tree as head_bwd_dw_kernel — bit-identical outputs — with
+// the loads arranged so that HBM requests stay in flight across the MFMAs:
+//   * a K-loop stage is D 64-row sub-stages (D * 8 KB of logits per
+//     block); the logits chunks and (coef, lse, y) rows of the next TWO
+//     stages are in registers or in flight: stage S+2 is issued before
+//     stage S's MFMAs and consumed after stage S+1's, so the loads also
+//     cover the G arithmetic and the barrier.
+//   * wave -> tile map is [64 labels x 16 EP] (was [16 labels x 64 EP]).
+//     Per accumulator the MFMA sequence is unchanged (k ascending: a0*b0
+//     then a1*b1 per 64-row sub-stage), but a wave needs only TWO global B
+//     fragments per sub-stage instead of eight, so a whole stage's B
+//     fragments fit in registers and the cv image is read once per block
+//     instead of four times (L2 traffic 1.16 GB -> 0.29 GB at top11); the
+//     extra A-fragment reads come from LDS.
+//   * issue order per stage: B fragments of THIS stage, then the logits
+//     prefetch of stage S+2, then a counted wait for the B fragments only —
+//     vmcnt counts in issue order, so the prefetch stays outstanding
+//     through the MFMAs.
+//   * every load is unconditional with the row / label chunk / image
+//     sub-stage clamped into its tensor; the guard selects the result of
+//     the arithmetic, so G of an invalid row or label chunk is exactly zero.
+//     Sub-stages past B multiply an all-zero G image (acc unchanged).
+//   * VAR (the C2V_HBDW_VARIANT phase-isolation bits) is a template
+//     parameter: the production instantiation has no branch around a load.
+// The staging registers are constant-indexed arrays under full unrolls
+// (registers, not scratch: the resource report shows 0 scratch).
+template <int D, int VAR>
+__global__ __launch_bounds__(512, 4) void head_bwd_dw_pipe_kernel(
+    const bf16* __restrict__ logits, const bf16* __restrict__ cvimg,
+    const float* __restrict__ coef_lse, bf16* __restrict__ dw,
+    float* __restrict__ dbias, long B, long L) {
+  static_assert(D >= 1 && D <= 2, "sub-stages per stage (3 and 4 spill)");
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wave = threadIdx.x / WAVE;
+  const long l0 = (long)blockIdx.x * HB_LB;
+  const int krow = threadIdx.x >> 3;        // 0..63: batch row within sub-stage
+  const int col8 = (threadIdx.x & 7) * 8;   // 0..56: label chunk start
+
+  // dynamic LDS: G images [2 buf][D][2 ksub][4 label tiles][HB_NSTR] bf16,
+  // reused as the dbias reduction scratch red[64][65] after the K-loop,
+  // then red2[8][65] f32
+  extern __shared__ __attribute__((aligned(16))) char hbp_smem[];
+  bf16* img = (bf16*)hbp_smem;
+  float* red = (float*)hbp_smem;
+  constexpr int SUBSZ = 2 * 4 * HB_NSTR;  // one sub-stage image (elements)
+  constexpr int IMGB = 2 * D * SUBSZ * 2;
+  constexpr int REDB = HB_ROWS * (HB_LB + 1) * 4;
+  float* red2 = (float*)(hbp_smem + (IMGB > REDB ? IMGB : REDB));
+
+  const int n = col8 >> 4;
+  const int base_l = col8 & 15;
+  const int ksub = krow >> 5;
+  const int kgrp = (krow >> 3) & 3;
+  const int jslot = krow & 7;
+  const long lc = l0 + col8;
+  const bool lok = lc < L;             // L % 8 == 0: chunk fully in bounds
+  const long lcc = lok ? lc : L - 8;   // clamped load address
+  const long nsub = (B + HB_ROWS - 1) / HB_ROWS;
+  const long nst = (nsub + D - 1) / D;
+
+  f32x4 db0 = {0.f, 0.f, 0.f, 0.f};
+  f32x4 db1 = {0.f, 0.f, 0.f, 0.f};
+  const bf16x8 zero8 = {};
+
+  // two staging register sets: stage t's logits chunks and (coef, lse, y)
+  // rows live in set t & 1 (named, swapped by unrolling the loop by two)
+  bf16x8 lvA[D], lvB[D];
+  hb_meta3 mtA[D], mtB[D];  // 12 of the row's 16 bytes
+  // cvimg layout: [k-chunk][8 nt][64 lanes][8]; this wave's EP tile = wave
+  const bf16* cbase = cvimg + (long)wave * 512 + (long)lane * 8;
+  // this thread's slot in a sub-stage G image
+  const int woff = (ksub * 4 + n) * HB_NSTR + (base_l + kgrp * 16) * 8 + jslot;
+
+// the (coef, lse, y) rows first (L2 hits), then the logits chunks (HBM)
+#define DWP_LOADL(lv, meta, S)                                             \
+  _Pragma("unroll") for (int i = 0; i < D; ++i) {                          \
+    if (VAR & 4) {                                                         \
+      meta[i] = hb_meta3{0.f, 0.f, 0.f};                                   \
+    } else {                                                               \
+      const long row_ = min(((S) * D + i) * HB_ROWS + krow, B - 1);        \
+      meta[i] = *(const hb_meta3*)(coef_lse + 4 * row_);                   \
+    }                                                                      \
+  }                                                                        \
+  __builtin_amdgcn_sched_barrier(0);                                       \
+  _Pragma("unroll") for (int i = 0; i < D; ++i) {                          \
+    if (VAR & 4) {                                                         \
+      lv[i] = zero8;                                                       \
+    } else {                                                               \
+      const long row_ = min(((S) * D + i) * HB_ROWS + krow, B - 1);        \
+      lv[i] = *(const bf16x8*)(logits + row_ * L + lcc);                   \
+    }                                                                      \
+  }
+
+// branch-free on purpose: the guard selects the result, so the arithmetic
+// sits in the loop's one basic block and the loads cannot be sunk into it
+#define DWP_WRITE(lv, meta, S, buf)                                        \
+  _Pragma("unroll") for (int i = 0; i < D; ++i) {                          \
+    const bool rok_ =                                                      \
+        ((S) * D + i) * HB_ROWS + krow < B && lok && !(VAR & 4);           \
+    bf16x8 gv;                                                             \
+    const float coef_ = meta[i].coef;                                      \
+    const float lse_ = meta[i].lse;                                        \
+    const long y_ = (long)meta[i].yf;                                      \
+    _Pragma("unroll") for (int j = 0; j < 8; ++j) {                        \
+      const float x_ = bf2f(lv[i][j]) - lse_;                              \
+      float g_ = coef_ * ((VAR & 8) ? x_ : __expf(x_));                    \
+      if (lc + j == y_) g_ -= coef_;                                       \
+      const bf16 gb_ = rok_ ? f2bf(g_) : zero8[0];                         \
+      gv[j] = gb_;                                                         \
+      if (j < 4) db0[j & 3] += rok_ ? bf2f(gb_) : 0.f;                     \
+      else db1[j & 3] += rok_ ? bf2f(gb_) : 0.f;                           \
+    }                                                                      \
+    bf16* dst_ = img + ((buf) * D + i) * SUBSZ + woff;                     \
+    _Pragma("unroll") for (int j = 0; j < 8; ++j) dst_[j * 8] = gv[j];     \
+  }
+
+  f32x4 acc[4];  // [label tile]
+#pragma unroll
+  for (int lt = 0; lt < 4; ++lt) acc[lt] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+#define DWP_LOADB(S)                                                       \
+  bf16x8 bq0[D], bq1[D];                                                   \
+  _Pragma("unroll") for (int i = 0; i < D; ++i) {                          \
+    if (VAR & 2) {                                                         \
+      bq0[i] = zero8;                                                      \
+      bq1[i] = zero8;                                                      \
+    } else {                                                               \
+      const bf16* p_ = cbase + min((S) * D + i, nsub - 1) * (16 * 512);    \
+      bq0[i] = *(const bf16x8*)(p_);                                       \
+      bq1[i] = *(const bf16x8*)(p_ + 8 * 512);                             \
+    }                                                                      \
+  }
+
+#define DWP_MMA(buf)                                                       \
+  {                                                                        \
+    const bf16* ib = img + (buf) * D * SUBSZ + lane * 8;                   \
+    _Pragma("unroll") for (int i = 0; i < D; ++i) {                        \
+      bf16x8 a0[4], a1[4];                                                 \
+      _Pragma("unroll") for (int lt = 0; lt < 4; ++lt) {                   \
+        a0[lt] = *(const bf16x8*)(ib + (i * 8 + lt) * HB_NSTR);            \
+        a1[lt] = *(const bf16x8*)(ib + (i * 8 + 4 + lt) * HB_NSTR);        \
+      }                                                                    \
+      if (!(VAR & 16)) {                                                   \
+        _Pragma("unroll") for (int lt = 0; lt < 4; ++lt)                   \
+            acc[lt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(             \
+                a0[lt], bq0[i], acc[lt], 0, 0, 0);                         \
+        _Pragma("unroll") for (int lt = 0; lt < 4; ++lt)                   \
+            acc[lt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(             \
+                a1[lt], bq1[i], acc[lt], 0, 0, 0);                         \
+      } else {                                                             \
+        _Pragma("unroll") for (int lt = 0; lt < 4; ++lt)                   \
+            acc[lt][0] += bf2f(a0[lt][0]) + bf2f(a1[lt][0]) +              \
+                          bf2f(bq0[i][0]) + bf2f(bq1[i][0]);               \
+      }                                                                    \
+    }                                                                      \
+  }
+
+// one stage: this stage's B fragments first, then the logits of the stage
+// after next (into the set the previous G write just freed); the wait in
+// front of the MFMAs covers the B fragments (and the older, next-stage
+// logits) only.  The next stage's G image is written from the other set.
+#define DWP_BODY(S, lvN, mtN, lvW, mtW, bufc)                              \
+  {                                                                        \
+    DWP_LOADB(S)                                                           \
+    __builtin_amdgcn_sched_barrier(0);                                     \
+    DWP_LOADL(lvN, mtN, (S) + 2)                                           \
+    __builtin_amdgcn_sched_barrier(0);                                     \
+    DWP_MMA(bufc)                                                          \
+    __builtin_amdgcn_sched_barrier(0);                                     \
+    if ((S) + 1 < nst2) {                                                  \
+      DWP_WRITE(lvW, mtW, (S) + 1, (bufc) ^ 1)                             \
+    }                                                                      \
+    __syncthreads();                                                       \
+  }
+
+  DWP_LOADL(lvA, mtA, 0L)
+  DWP_LOADL(lvB, mtB, 1L)
+  DWP_WRITE(lvA, mtA, 0L, 0)
+  __syncthreads();
+
+  // the loop body is two whole stages, straight-line (a conditional
+  // second stage makes a join where the compiler drains every load); an
+  // odd stage count runs one all-zero stage: zero G image, acc unchanged
+  const long nst2 = (nst + 1) & ~1L;
+  for (long S = 0; S < nst2; S += 2) {
+    DWP_BODY(S, lvA, mtA, lvB, mtB, 0)
+    DWP_BODY(S + 1, lvB, mtB, lvA, mtA, 1)
+  }
+#undef DWP_BODY
+#undef DWP_LOADB
+#undef DWP_MMA
+#undef DWP_LOADL
+#undef DWP_WRITE
+
+  // dW: each wave owns [64 labels x 16 EP] of the block's [64, 128] tile
+#pragma unroll
+  for (int lt = 0; lt < 4; ++lt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const long lrow_ = l0 + lt * 16 + (lane >> 4) * 4 + r;
+      if (lrow_ < L && !(VAR & 1))
+        dw[lrow_ * 128 + wave * 16 + (lane & 15)] = f2bf(acc[lt][r]);
+    }
+
+  // dbias: the head_bwd_dw_kernel tree, unchanged (red[krow][label],
+  // stride 65)
+#pragma unroll
+  for (int j = 0; j < 4; ++j) red[krow * (HB_LB + 1) + col8 + j] = db0[j];
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    red[krow * (HB_LB + 1) + col8 + 4 + j] = db1[j];
+  __syncthreads();
+  {
+    const int lbl = threadIdx.x & 63;
+    const int kg0 = (threadIdx.x >> 6) * 8;
+    float p = 0.f;
+#pragma unroll
+    for (int kg = 0; kg < 8; ++kg) p += red[(kg0 + kg) * (HB_LB + 1) + lbl];
+    red2[(threadIdx.x >> 6) * (HB_LB + 1) + lbl] = p;
+  }
+  __syncthreads();
+  if (threadIdx.x < 64 && l0 + threadIdx.x < L && !(VAR & 1)) {
+    float s2 = 0.f;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) s2 += red2[q * (HB_LB + 1) + threadIdx.x];
+    dbias[l0 + threadIdx.x] = s2;
   }
 }
 
@@ -507,6 +746,131 @@ __global__ __launch_bounds__(512) void head_bwd_dcv_kernel(
   }
 }
 
+// PIPELINED head_bwd_dcv: same tiling, slabs, swizzle and per-accumulator
+// MFMA order (sub-stage ascending, kk ascending) as head_bwd_dcv_kernel —
+// bit-identical partials — with split staging: while sub-stage s runs its
+// 32 MFMAs per wave, sub-stage s+1's four logits fragments and its four
+// 16-B pieces of the W image are already in flight into registers, issued
+// together.  Fragment loads are unconditional with row and label offset
+// clamped into [0, B*L); the fragment is zeroed afterwards where the row
+// or the label chunk is out of range.
+// DBUF=1 double-buffers the W image in LDS (64 KB, one barrier per
+// sub-stage); DBUF=0 keeps the single 32-KB buffer and the second barrier.
+template <int DBUF>
+__global__ __launch_bounds__(512, 4) void head_bwd_dcv_pipe_kernel(
+    const bf16* __restrict__ logits, const bf16* __restrict__ wimg,
+    const float* __restrict__ coef_lse, float* __restrict__ partials, long B,
+    long L, int chunk, int GYB) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wave = threadIdx.x / WAVE;
+  const int total = gridDim.x;
+  const int lin = (total % 8 == 0)
+      ? (int)(blockIdx.x % 8) * (total / 8) + (int)blockIdx.x / 8
+      : (int)blockIdx.x;
+  const int by = lin % GYB;
+  const int sc = lin / GYB;
+  const long bt0 = (long)by * 128;
+  const int kj = (lane >> 4) * 8;
+
+  const long row = bt0 + wave * 16 + (lane & 15);
+  const bool aok = row < B;
+  float coef = 0.f, lseb = 0.f;
+  long y = -1;
+  if (aok) {
+    const f32x4 meta = *(const f32x4*)(coef_lse + 4 * row);
+    coef = meta[0];
+    lseb = meta[1];
+    y = (long)meta[2];
+  }
+  const bf16* ap = logits + min(row, B - 1) * L;  // clamped row
+
+  // 128-label sub-stages of the W image: [4 kc][8 nt][64 lanes][8] each
+  __shared__ bf16 wst[DBUF ? 2 : 1][4 * 8 * 512];
+
+  f32x4 acc[8];
+#pragma unroll
+  for (int nt = 0; nt < 8; ++nt) acc[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const bf16x8 zero8 = {};
+
+  // sub-stages of this block that start inside L (>= 1: sc * chunk < L)
+  const long lbase = (long)sc * chunk;
+  const int nv = (int)min((long)(chunk / 128), (L - lbase + 127) / 128);
+
+  bf16x8 an[4];  // next sub-stage's logits fragments
+  bf16x8 wr[4];  // next sub-stage's W image pieces
+
+#define DCVP_LOAD(l0_)                                                     \
+  do {                                                                     \
+    _Pragma("unroll") for (int kk = 0; kk < 4; ++kk)                       \
+        an[kk] = *(const bf16x8*)(ap +                                     \
+                                  min((l0_) + kk * 32 + kj, L - 8));       \
+    const bf16* src_ = wimg + ((l0_) >> 5) * 4096 + threadIdx.x * 8;       \
+    _Pragma("unroll") for (int i = 0; i < 4; ++i)                          \
+        wr[i] = *(const bf16x8*)(src_ + i * 4096);                         \
+  } while (0)
+
+#define DCVP_STAGE(b)                                                      \
+  _Pragma("unroll") for (int i = 0; i < 4; ++i)                            \
+      *(bf16x8*)&wst[b][(threadIdx.x + i * 512) * 8] = wr[i]
+
+  DCVP_LOAD(lbase);
+  DCVP_STAGE(0);
+  __syncthreads();
+
+  for (int s = 0; s < nv; ++s) {
+    const long l0 = lbase + (long)s * 128;
+    const int cur = DBUF ? (s & 1) : 0;
+    const bool more = s + 1 < nv;  // block-uniform
+    // the landed fragments move out of the prefetch registers so the next
+    // sub-stage's loads are in flight before the G arithmetic starts
+    bf16x8 ac[4];
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) ac[kk] = an[kk];
+    if (more) DCVP_LOAD(l0 + 128);
+    bf16x8 a[4];
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+      const long lc = l0 + kk * 32 + kj;
+      a[kk] = zero8;
+      if (aok && lc < L) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          float gg = coef * __expf(bf2f(ac[kk][j]) - lseb);
+          if (lc + j == y) gg -= coef;
+          a[kk][j] = f2bf(gg);
+        }
+      }
+    }
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+      bf16x8 b[8];
+#pragma unroll
+      for (int nt = 0; nt < 8; ++nt)
+        b[nt] = *(const bf16x8*)&wst[cur][(kk * 8 + nt) * 512 + lane * 8];
+#pragma unroll
+      for (int nt = 0; nt < 8; ++nt)
+        acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[kk], b[nt],
+                                                          acc[nt], 0, 0, 0);
+    }
+    if (!DBUF) __syncthreads();
+    if (more) DCVP_STAGE(DBUF ? (cur ^ 1) : 0);
+    __syncthreads();
+  }
+#undef DCVP_LOAD
+#undef DCVP_STAGE
+
+  float* slab = partials + (long)sc * B * 128;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const long grow = bt0 + wave * 16 + (lane >> 4) * 4 + r;
+    if (grow < B) {
+#pragma unroll
+      for (int nt = 0; nt < 8; ++nt)
+        slab[grow * 128 + nt * 16 + (lane & 15)] = acc[nt][r];
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------
 // STREAMING variant of the dcv kernel: the logits tensor is never READ —
 // each wave recomputes its [16 batch x 128 label] logits tile with a first
@@ -695,6 +1059,70 @@ void launch_head_bwd_dcv(const void* logits, const void* wimg,
   head_bwd_dcv_kernel<<<GYB * split, 512, 0, stream>>>(
       (const bf16*)logits, (const bf16*)wimg, coef_lse, partials, B, L,
       chunk, GYB);
+}
+
+// LDS bytes of head_bwd_dw_pipe_kernel<D>: G images (or the dbias scratch,
+// whichever is larger) + red2
+static int hbp_dw_smem(int D) {
+  const int imgb = 2 * D * 2 * 4 * HB_NSTR * 2;
+  const int redb = HB_ROWS * (HB_LB + 1) * 4;
+  return (imgb > redb ? imgb : redb) + 8 * (HB_LB + 1) * 4;
+}
+
+// depth: 64-row sub-stages per stage D (1 or 2; two stages are prefetched,
+// so 2 * D sub-stages of logits are in flight per thread); 0 =
+// C2V_HB_DW_DEPTH or the shipped default.  Returns false for an
+// unsupported depth / variant combination (the diagnostic variants exist
+// at the shipped depth only, variant 16 at D = 1).
+bool launch_head_bwd_dw_pipe(const void* logits, const void* cvimg,
+                             const float* coef_lse, void* dw, float* dbias,
+                             long B, long L, int depth, hipStream_t stream) {
+  if (depth == 0) {
+    const char* de = getenv("C2V_HB_DW_DEPTH");
+    depth = de ? atoi(de) : HB_DW_DEPTH;
+  }
+  const char* ve = getenv("C2V_HBDW_VARIANT");
+  const int variant = ve ? atoi(ve) : 0;
+  const int grid = (int)((L + HB_LB - 1) / HB_LB);
+#define DWP_CASE(d, v)                                                     \
+  if (depth == d && variant == v) {                                        \
+    head_bwd_dw_pipe_kernel<d, v><<<grid, 512, hbp_dw_smem(d), stream>>>(  \
+        (const bf16*)logits, (const bf16*)cvimg, coef_lse, (bf16*)dw,      \
+        dbias, B, L);                                                      \
+    return true;                                                           \
+  }
+  DWP_CASE(1, 0) DWP_CASE(2, 0)
+  // diagnostic instantiations (phase isolation) at the shipped depth
+  DWP_CASE(HB_DW_DEPTH, 1) DWP_CASE(HB_DW_DEPTH, 2) DWP_CASE(HB_DW_DEPTH, 4)
+  DWP_CASE(HB_DW_DEPTH, 6) DWP_CASE(HB_DW_DEPTH, 8)
+  // the no-MFMA variant spills at D = 2 (the cheap accumulate keeps every
+  // A fragment live at once); it exists at D = 1
+  if (variant == 16) depth = 1;
+  DWP_CASE(1, 16)
+#undef DWP_CASE
+  return false;
+}
+
+// dbuf: 1 = double-buffered W image, 0 = single buffer, -1 =
+// C2V_HB_DCV_DBUF or the default
+void launch_head_bwd_dcv_pipe(const void* logits, const void* wimg,
+                              const float* coef_lse, float* partials, long B,
+                              long L, int chunk, int dbuf,
+                              hipStream_t stream) {
+  if (dbuf < 0) {
+    const char* de = getenv("C2V_HB_DCV_DBUF");
+    dbuf = de ? atoi(de) : HB_DCV_DBUF;
+  }
+  const int GYB = (int)((B + 127) / 128);
+  const int split = (int)((L + chunk - 1) / chunk);
+  if (dbuf)
+    head_bwd_dcv_pipe_kernel<1><<<GYB * split, 512, 0, stream>>>(
+        (const bf16*)logits, (const bf16*)wimg, coef_lse, partials, B, L,
+        chunk, GYB);
+  else
+    head_bwd_dcv_pipe_kernel<0><<<GYB * split, 512, 0, stream>>>(
+        (const bf16*)logits, (const bf16*)wimg, coef_lse, partials, B, L,
+        chunk, GYB);
 }
 
 void launch_head_bwd_dcv_rc(const void* cvimg_a, const void* wimg_a,

@@ -13,6 +13,8 @@
 //   B: lane l holds B[k = (l>>4)*8 + j][col = l&15] -> dZ[m][ep]
 //   C/D: lane l, reg r holds C[i = (l>>4)*4 + r][col = l&15]
 
+#include <cstdlib>
+
 #include "common.h"
 
 // GATHER=1: the X operand is re-gathered from the embedding tables during
@@ -172,6 +174,159 @@ __global__ __launch_bounds__(512, MINW) void wgrad_kernel(
   }
 }
 
+// PIPELINED wgrad (X given, no gather): the same slabs, the same
+// per-accumulator MFMA order (32-row K-steps ascending) — bit-identical
+// partials — with H 32-row K-steps staged per loop iteration, so H times
+// the bytes are in flight per CU while the MFMAs run (one block per CU:
+// 28 KB per 32-row step at KP = 320).  Rows past the block's range stage
+// as zeros, as before; a zero K-step leaves the accumulators unchanged.
+template <int NT, int IT, int H>
+__global__ __launch_bounds__(512) void wgrad_pipe_kernel(
+    const bf16* __restrict__ X, const bf16* __restrict__ dZ,
+    float* __restrict__ partials, long M, int KP, int EP,
+    long rows_per_block) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wave = threadIdx.x / WAVE;
+  const long m0 = (long)blockIdx.x * rows_per_block;
+  const long m1 = min(m0 + rows_per_block, M);
+
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  // fragment images per 32-row K-step, double-buffered per stage:
+  //   x_img [2][H][KP/16 tiles][NSTRIDE], dz_img [2][H][NT][NSTRIDE]
+  const size_t NSTRIDE = 64 * 8 + 8;
+  const size_t xsz = (size_t)(KP / 16) * NSTRIDE;
+  const size_t dsz = (size_t)NT * NSTRIDE;
+  bf16* x_img = (bf16*)smem;
+  bf16* dz_img = x_img + 2 * H * xsz;
+
+  f32x4 acc[IT][NT];
+#pragma unroll
+  for (int i = 0; i < IT; ++i)
+#pragma unroll
+    for (int n = 0; n < NT; ++n) acc[i][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  constexpr int CX = 4;  // max 16-B x chunks/thread/K-step (KP <= 512)
+  uint4 xr[H][CX];
+  uint4 dzr[H];
+  auto stage_load = [&](long mb) {
+    const int chunks_x = 32 * KP / 8;
+#pragma unroll
+    for (int h = 0; h < H; ++h) {
+      const long mh = mb + h * 32;
+      const int rows = (int)max((long)0, min((long)32, m1 - mh));
+#pragma unroll
+      for (int i = 0; i < CX; ++i) {
+        const int c = threadIdx.x + i * 512;
+        uint4 v = {0, 0, 0, 0};
+        if (c < chunks_x) {
+          const int krow = c / (KP / 8);
+          const int col8 = (c % (KP / 8)) * 8;
+          if (krow < rows) v = *(const uint4*)(X + (mh + krow) * KP + col8);
+        }
+        xr[h][i] = v;
+      }
+      {
+        const int c = threadIdx.x;
+        uint4 v = {0, 0, 0, 0};
+        if (c < 32 * EP / 8) {
+          const int krow = c / (EP / 8);
+          if (krow < rows)
+            v = *(const uint4*)(dZ + (mh + krow) * EP + (c % (EP / 8)) * 8);
+        }
+        dzr[h] = v;
+      }
+    }
+  };
+  auto stage_write = [&](int buf) {
+    const int chunks_x = 32 * KP / 8;
+#pragma unroll
+    for (int h = 0; h < H; ++h) {
+#pragma unroll
+      for (int i = 0; i < CX; ++i) {
+        const int c = threadIdx.x + i * 512;
+        if (c < chunks_x) {
+          const int krow = c / (KP / 8);
+          const int col8 = (c % (KP / 8)) * 8;
+          bf16 vals[8];
+          *(uint4*)vals = xr[h][i];
+          const int n = col8 / 16;
+          const int base_l = (col8 & 15) + (krow >> 3) * 16;
+          const int jslot = krow & 7;
+          bf16* dst = x_img + (buf * H + h) * xsz + (size_t)n * NSTRIDE;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) dst[(base_l + j) * 8 + jslot] = vals[j];
+        }
+      }
+      {
+        const int c = threadIdx.x;
+        if (c < 32 * EP / 8) {
+          const int krow = c / (EP / 8);
+          const int col8 = (c % (EP / 8)) * 8;
+          bf16 vals[8];
+          *(uint4*)vals = dzr[h];
+          const int n = col8 / 16;
+          const int base_l = (col8 & 15) + (krow >> 3) * 16;
+          const int jslot = krow & 7;
+          bf16* dst = dz_img + (buf * H + h) * dsz + (size_t)n * NSTRIDE;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) dst[(base_l + j) * 8 + jslot] = vals[j];
+        }
+      }
+    }
+  };
+
+  if (m0 < m1) {
+    stage_load(m0);
+    stage_write(0);
+    __syncthreads();
+  }
+  int buf = 0;
+  for (long mb = m0; mb < m1; mb += 32 * H) {
+    const bool more = mb + 32 * H < m1;
+    if (more) stage_load(mb + 32 * H);
+#pragma unroll
+    for (int h = 0; h < H; ++h) {
+      bf16x8 bfrag[NT];
+#pragma unroll
+      for (int n = 0; n < NT; ++n)
+        bfrag[n] = *(const bf16x8*)(dz_img + (buf * H + h) * dsz +
+                                    (size_t)n * NSTRIDE + (size_t)lane * 8);
+#pragma unroll
+      for (int i = 0; i < IT; ++i) {
+        const int itile = IT * wave + i;
+        if (itile >= KP / 16) break;
+        const bf16x8 a = *(const bf16x8*)(x_img + (buf * H + h) * xsz +
+                                          (size_t)itile * NSTRIDE +
+                                          (size_t)lane * 8);
+#pragma unroll
+        for (int n = 0; n < NT; ++n)
+          acc[i][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              a, bfrag[n], acc[i][n], 0, 0, 0);
+      }
+    }
+    if (more) stage_write(buf ^ 1);
+    buf ^= 1;
+    __syncthreads();
+  }
+
+  // write this block's fp32 partial slab [KP, EP]
+  float* slab = partials + (size_t)blockIdx.x * KP * EP;
+#pragma unroll
+  for (int i = 0; i < IT; ++i) {
+    const int itile = IT * wave + i;
+    if (itile >= KP / 16) break;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = itile * 16 + (lane >> 4) * 4 + r;
+#pragma unroll
+      for (int n = 0; n < NT; ++n) {
+        const int col = n * 16 + (lane & 15);
+        slab[(size_t)row * EP + col] = acc[i][n][r];
+      }
+    }
+  }
+}
+
 extern "C" {
 
 void launch_wgrad_impl(const void* X, const void* dZ, float* partials,
@@ -225,6 +380,41 @@ void launch_wgrad(const void* X, const void* dZ, float* partials, long M,
                   int KP, int EP, int nblocks, hipStream_t stream) {
   launch_wgrad_impl(X, dZ, partials, M, KP, EP, nblocks, nullptr, nullptr,
                     nullptr, nullptr, nullptr, 0, 0, stream);
+}
+
+// Pipelined split-K wgrad: h = 32-row K-steps per stage (2 or 3), 0 =
+// C2V_WGRAD_DEPTH or the shipped default.  Returns false where there is no
+// instantiation (callers then use launch_wgrad).
+bool launch_wgrad_pipe(const void* X, const void* dZ, float* partials, long M,
+                       int KP, int EP, int nblocks, int h,
+                       hipStream_t stream) {
+  if (h == 0) {
+    const char* de = getenv("C2V_WGRAD_DEPTH");
+    h = de ? atoi(de) : 2;
+  }
+  const long rows_per_block = ((M + nblocks - 1) / nblocks + 31) / 32 * 32;
+  const int NT = EP / 16;
+  const int IT = (KP / 16 + 7) / 8;
+  if (EP % 16 || KP % 16 || EP > 128 || KP > 512) return false;
+  const int smem = 2 * h * ((KP / 16) + NT) * (64 * 8 + 8) * 2;
+  if (smem > 160 * 1024) return false;
+#define WPCASE(nt, it, hh)                                                   \
+  if (NT == nt && IT == it && h == hh) {                                     \
+    auto kern = wgrad_pipe_kernel<nt, it, hh>;                               \
+    static int attr_smem = 0; /* > 64 KB of dynamic LDS is opt-in */         \
+    if (smem > 65536 && smem > attr_smem) {                                  \
+      hipFuncSetAttribute((const void*)kern,                                 \
+                          hipFuncAttributeMaxDynamicSharedMemorySize, smem); \
+      attr_smem = smem;                                                      \
+    }                                                                        \
+    kern<<<nblocks, 512, smem, stream>>>((const bf16*)X, (const bf16*)dZ,    \
+                                         partials, M, KP, EP,                \
+                                         rows_per_block);                    \
+    return true;                                                             \
+  }
+  WPCASE(8, 1, 2) WPCASE(8, 2, 2) WPCASE(8, 3, 2) WPCASE(8, 4, 2)
+#undef WPCASE
+  return false;
 }
 
 void launch_wgrad_gather(const int* starts, const int* paths,

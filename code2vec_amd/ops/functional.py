@@ -68,6 +68,18 @@ FUSED_HEAD = os.environ.get("C2V_FUSED_HEAD", "1") == "1"
 FUSED_CAP = os.environ.get("C2V_FUSED_CAP", "1") == "1"
 # one-launch reductions; each =0 reverts to the chain it replaced
 _WGRAD_REDUCE = os.environ.get("C2V_WGRAD_REDUCE", "1") == "1"  # sum+t+cast
+# Pipelined head backward (head_bwd_dw_pipe / head_bwd_dcv_pipe) and
+# split-K wgrad (wgrad_pipe): the same arithmetic in the same order as the
+# kernels they replace — bit-identical outputs — with the loads kept in
+# flight across the MFMAs.  Only the dW/dbias kernel measured faster
+# (83 -> 60 us at top11) and is on by default; the dcv and wgrad variants
+# measured 2-4% SLOWER than their kernels on the same buffers (PERF.md) and
+# ship off.  C2V_HB_PIPE=0 reverts every head kernel, C2V_HB_PIPE_DW /
+# C2V_HB_PIPE_DCV / C2V_WGRAD_PIPE = 0 | 1 select each part.
+_HB_PIPE = os.environ.get("C2V_HB_PIPE", "1") == "1"
+_HB_PIPE_DW = _HB_PIPE and os.environ.get("C2V_HB_PIPE_DW", "1") == "1"
+_HB_PIPE_DCV = _HB_PIPE and os.environ.get("C2V_HB_PIPE_DCV", "0") == "1"
+_WGRAD_PIPE = os.environ.get("C2V_WGRAD_PIPE", "0") == "1"
 _SLAB_SUM2 = os.environ.get("C2V_SLAB_SUM2", "1") == "1"  # dgamma+dbeta
 # loss partials -> acc and acc[0]/acc[1] in one launch.  Same bits, one
 # launch fewer, but its step-time gain could not be told from the
@@ -701,7 +713,11 @@ def _combiner_dx_dw(x, w, dz):
         nsplit = 256
         partials = torch.empty(nsplit, KP, EP, dtype=torch.float32,
                                device=x.device)
-        ext().wgrad(x, dz, partials)
+        # two 32-row K-steps of fragment images must fit the 160-KB LDS
+        if _WGRAD_PIPE and EP == 128 and KP % 16 == 0 and KP <= 480:
+            ext().wgrad_pipe(x, dz, partials, 0)
+        else:
+            ext().wgrad(x, dz, partials)
         dw = _wgrad_reduce(partials)
     else:
         dw = (x.t() @ dz).t().contiguous()
@@ -1290,7 +1306,10 @@ class FusedHeadLoss(torch.autograd.Function):
         ext().swizzle_cv(cv.contiguous(), cvimg)
         dw = torch.empty(L, 128, dtype=torch.bfloat16, device=dev)
         dbias = torch.empty(L, dtype=torch.float32, device=dev)
-        ext().head_bwd_dw(logits, cvimg, coef_lse, dw, dbias)
+        if _HB_PIPE_DW:
+            ext().head_bwd_dw_pipe(logits, cvimg, coef_lse, dw, dbias, 0)
+        else:
+            ext().head_bwd_dw(logits, cvimg, coef_lse, dw, dbias)
         # dcv (batch-major split-K): label chunk balances split-K slab
         # traffic against grid width (A/B-swept: 1024 beats 512 by ~30
         # us/step at top11; 4096 at java-large keeps slabs ~33 MB).  W is
@@ -1320,6 +1339,9 @@ class FusedHeadLoss(torch.autograd.Function):
             ext().head_bwd_dcv_rc(cvimg_a, wimg_a, wimg,
                                   bias.detach().float().contiguous(),
                                   coef_lse, partials, B, L, chunk)
+        elif _HB_PIPE_DCV:
+            ext().head_bwd_dcv_pipe(logits, wimg, coef_lse, partials, chunk,
+                                    -1)
         else:
             ext().head_bwd_dcv(logits, wimg, coef_lse, partials, chunk)
         dcv = torch.empty(B, 128, dtype=torch.bfloat16, device=dev)

@@ -10,7 +10,8 @@ env vars read by ops/functional.py.  Usage (on a GPU box):
 recomputing combiner backward vs what they replace) and ``group_tables``
 (both tables' counting sort: per-table chains vs the one merged chain) and
 ``attn_stream`` (streaming attention forward/backward and the combiner's
-score-emitting flush vs the tiled kernels) are
+score-emitting flush vs the tiled kernels) and ``head_bwd_pipe`` (the
+pipelined head backward and wgrad kernels vs the ones they replace) are
 not in the default set; asked for alone they skip building the model-shaped
 operands.
 """
@@ -353,6 +354,89 @@ def bench_attn_stream(dev, results, rounds=5):
         results[f"{k} min"] = vals[0]
 
 
+def bench_head_bwd_pipe(dev, results, rounds=5):
+    """The pipelined head backward and wgrad kernels against the ones they
+    replace on the SAME buffers, alternating within each round (median /
+    min), at the top11 shapes: head B=1024, L=72,416 (dw + dbias, dcv
+    slabs at chunk 1024) and wgrad M=204,800, KP=320, EP=128, 256 slabs.
+    Every depth / buffering instantiation is timed (the sweep), and with
+    C2V_KBENCH_HBDW_VARIANTS=1 also the phase-isolation variants of the old
+    and the new dw kernel (4 = no logits loads, 2 = no B loads, 16 = no
+    MFMA)."""
+    from code2vec_amd.ops import ext
+
+    g = torch.Generator(device=dev).manual_seed(0)
+    B, L, EP = 1024, 72416, 128
+    logits = (torch.randn(B, L, generator=g, device=dev) * 3.0).to(
+        torch.bfloat16)
+    label = torch.randint(0, L, (B,), generator=g, device=dev)
+    weight = torch.rand(L, generator=g, device=dev) + 0.5
+    lse = torch.logsumexp(logits.float(), dim=1).contiguous()
+    acc = torch.stack([torch.zeros((), device=dev), weight[label].sum()])
+    coef_lse = torch.zeros(B, 4, device=dev)
+    ext().head_bwd_prep(label, weight, acc, torch.ones(1, device=dev), lse,
+                        coef_lse)
+    cv = (torch.randn(B, EP, generator=g, device=dev) * 0.5).to(
+        torch.bfloat16)
+    cvimg = torch.empty((B + 63) // 64 * 2, 8, 64, 8, dtype=torch.bfloat16,
+                        device=dev)
+    ext().swizzle_cv(cv, cvimg)
+    wout = (torch.randn(L, EP, generator=g, device=dev) * 0.05).to(
+        torch.bfloat16)
+    wimg = torch.empty((L + 127) // 128 * 4, 8, 64, 8, dtype=torch.bfloat16,
+                       device=dev)
+    ext().swizzle_cv(wout, wimg)
+    dw = torch.empty(L, EP, dtype=torch.bfloat16, device=dev)
+    dbias = torch.empty(L, device=dev)
+    chunk = 1024
+    partials = torch.empty((L + chunk - 1) // chunk, B, EP, device=dev)
+    M, KP = 204800, 320
+    x = torch.randn(M, KP, generator=g, device=dev).to(torch.bfloat16)
+    dz = (torch.randn(M, EP, generator=g, device=dev) * 0.3).to(
+        torch.bfloat16)
+    wpart = torch.empty(256, KP, EP, device=dev)
+
+    cases = {"head_bwd_dw": lambda: ext().head_bwd_dw(
+        logits, cvimg, coef_lse, dw, dbias)}
+    for d in (1, 2):
+        cases[f"head_bwd_dw_pipe D={d}"] = (
+            lambda d=d: ext().head_bwd_dw_pipe(logits, cvimg, coef_lse, dw,
+                                               dbias, d))
+    cases["head_bwd_dcv"] = lambda: ext().head_bwd_dcv(
+        logits, wimg, coef_lse, partials, chunk)
+    for b in (0, 1):
+        cases[f"head_bwd_dcv_pipe dbuf={b}"] = (
+            lambda b=b: ext().head_bwd_dcv_pipe(logits, wimg, coef_lse,
+                                                partials, chunk, b))
+    cases["wgrad"] = lambda: ext().wgrad(x, dz, wpart)
+    cases["wgrad_pipe H=2"] = lambda: ext().wgrad_pipe(x, dz, wpart, 2)
+
+    def with_variant(v, fn):
+        def run():
+            os.environ["C2V_HBDW_VARIANT"] = str(v)
+            try:
+                fn()
+            finally:
+                del os.environ["C2V_HBDW_VARIANT"]
+        return run
+
+    if os.environ.get("C2V_KBENCH_HBDW_VARIANTS") == "1":
+        for v in (4, 2, 16):
+            cases[f"head_bwd_dw variant={v}"] = with_variant(
+                v, cases["head_bwd_dw"])
+            cases[f"head_bwd_dw_pipe variant={v}"] = with_variant(
+                v, lambda: ext().head_bwd_dw_pipe(logits, cvimg, coef_lse,
+                                                  dw, dbias, 0))
+    t = {k: [] for k in cases}
+    for _ in range(rounds):
+        for k, fn in cases.items():
+            t[k].append(timeit(fn, iters=20))
+    for k, vals in t.items():
+        vals.sort()
+        results[f"{k} med"] = vals[rounds // 2]
+        results[f"{k} min"] = vals[0]
+
+
 def main():
     if "--help" in sys.argv or "-h" in sys.argv:
         print(__doc__.strip())
@@ -362,13 +446,16 @@ def main():
         return
     dev = torch.device("cuda:0")
     if sys.argv[1:] in (["row_topk"], ["table_adam"], ["bwd_fusions"],
-                        ["group_tables"], ["attn_stream"]):
+                        ["group_tables"], ["attn_stream"],
+                        ["head_bwd_pipe"]):
         # needs none of the model-shaped operands built below
         results = {}
         if sys.argv[1] == "row_topk":
             bench_row_topk(dev, results)
         elif sys.argv[1] == "attn_stream":
             bench_attn_stream(dev, results)
+        elif sys.argv[1] == "head_bwd_pipe":
+            bench_head_bwd_pipe(dev, results)
         elif sys.argv[1] == "bwd_fusions":
             bench_bwd_fusions(dev, results)
         elif sys.argv[1] == "group_tables":
