@@ -604,8 +604,12 @@ int launch_combiner_fwd_impl(const void* X, const void* W,
                          const float* att_a, float* raw_scores,
                          hipStream_t stream) {
   const int NT = EP / 16;
+  // MT = 1 is built for the gather kernels only: every other launch below
+  // is an MT = 2 kernel, and the grid and the LDS bounce tile must be sized
+  // for the kernel that runs (sized for MT = 1, waves 2 and 3 of an MT = 2
+  // block staged their rows past the allocation and flushed zeros)
   const char* mt_env = getenv("C2V_COMBINER_MT");
-  const int mt = (mt_env && mt_env[0] == '1') ? 1 : 2;
+  const int mt = (gather && mt_env && mt_env[0] == '1') ? 1 : 2;
   // Occupancy-forced register allocation (C2V_COMBINER_OCC=0/3/4): the
   // unconstrained build burns 230 VGPR+AGPR -> 2 waves/SIMD; with the
   // epilogue bounce aliased over the dead B buffer, LDS fits 4 blocks/CU
@@ -618,7 +622,6 @@ int launch_combiner_fwd_impl(const void* X, const void* W,
   const long grid = (M + mt * 64 - 1) / (mt * 64);
   const float inv1mp = p > 0.f ? 1.0f / (1.0f - p) : 1.0f;
   int epi = epilogue_mode;
-  (void)gather;
   const int bbuf = 2 * EP * 40 * (int)sizeof(bf16);
   int smem = 2 * EP * sizeof(float) + bbuf;
   if (epi == 1) {
