@@ -49,6 +49,22 @@ class EpochData:
         return self.starts.shape[0]
 
 
+@dataclass
+class PackedData:
+    """Methods with ALL their contexts, back to back (no padding): method i
+    owns the next ``lengths[i]`` entries of the flat index arrays."""
+
+    ids: List[int]
+    starts: np.ndarray   # [M] int32
+    paths: np.ndarray    # [M] int32
+    ends: np.ndarray     # [M] int32
+    lengths: np.ndarray  # [N] int64, every entry >= 1, sum == M
+    labels: np.ndarray   # [N] int64
+
+    def __len__(self) -> int:
+        return self.lengths.shape[0]
+
+
 def _filter_variable_aliases(aliases: dict) -> List[str]:
     return [a for a in aliases if a.startswith("@var_")]
 
@@ -370,6 +386,86 @@ class DatasetBuilder:
             starts=starts,
             paths=paths,
             ends=ends,
+            labels=np.asarray(labels, dtype=np.int64),
+        )
+
+    def build_packed(self, items: List[CodeItem], epoch: int = 0,
+                     stream: int = 1) -> PackedData:
+        """Every context of every item, in corpus order: no permutation, no
+        truncation, no padding (the inference layout of
+        ``forward_packed``).  @method_0 becomes @question as in
+        ``build_data``; the variable-name task gives one segment per @var
+        alias with ``_build_variable_rows``' filter.  A segment without
+        contexts becomes one PAD context (0, 0, 0): it is masked, so its
+        code vector is the one the padded path gives an all-pad row.
+
+        Only ``shuffle_variable_indexes`` draws random numbers, from a
+        generator seeded like ``build_data``'s; ``build_data`` makes its own
+        on every call, so its draws are not disturbed."""
+        reader = self.reader
+        q = reader.QUESTION_TOKEN_INDEX
+        label_stoi = reader.label_vocab.stoi
+        ids: List[int] = []
+        labels: List[int] = []
+        segments: List[np.ndarray] = []  # [n, 3] (start, path, end) each
+
+        if reader.infer_method:
+            method_token_index = reader.terminal_vocab.stoi.get(
+                "@method_0", -1)
+            for item in items:
+                seg = np.array(item.path_contexts, dtype=np.int32).reshape(
+                    -1, 3)
+                for col in (0, 2):
+                    seg[seg[:, col] == method_token_index, col] = q
+                ids.append(item.id)
+                labels.append(label_stoi[item.normalized_label])
+                segments.append(seg)
+
+        if reader.infer_variable:
+            rng = np.random.default_rng(
+                [self.seed, epoch, stream, self.rank])
+            term_stoi = reader.terminal_vocab.stoi
+            variable_indexes = np.asarray(reader.variable_indexes,
+                                          dtype=np.int32)
+            remap = {int(v): int(v) for v in variable_indexes}
+            for item in items:
+                alias_names = _filter_variable_aliases(item.aliases)
+                if not alias_names:
+                    continue
+                if reader.shuffle_variable_indexes:
+                    perm = rng.permutation(len(variable_indexes))
+                    remap = {
+                        int(k): int(variable_indexes[perm[i]])
+                        for i, k in enumerate(variable_indexes)
+                    }
+                pcs = np.asarray(item.path_contexts, dtype=np.int32).reshape(
+                    -1, 3)
+                for alias_name in alias_names:
+                    var_idx = term_stoi[alias_name]
+                    seg = pcs[(pcs[:, 0] == var_idx)
+                              | (pcs[:, 2] == var_idx)].copy()
+                    for col in (0, 2):
+                        own = seg[:, col] == var_idx
+                        if reader.shuffle_variable_indexes:
+                            for j in np.nonzero(~own)[0]:
+                                v = int(seg[j, col])
+                                seg[j, col] = remap.get(v, v)
+                        seg[own, col] = q
+                    ids.append(item.id)
+                    labels.append(label_stoi[item.aliases[alias_name]])
+                    segments.append(seg)
+
+        pad = np.zeros((1, 3), dtype=np.int32)
+        segments = [s if s.shape[0] else pad for s in segments]
+        flat = (np.concatenate(segments, axis=0) if segments
+                else np.empty((0, 3), dtype=np.int32))
+        return PackedData(
+            ids=ids,
+            starts=np.ascontiguousarray(flat[:, 0]),
+            paths=np.ascontiguousarray(flat[:, 1]),
+            ends=np.ascontiguousarray(flat[:, 2]),
+            lengths=np.asarray([s.shape[0] for s in segments],
+                               dtype=np.int64),
             labels=np.asarray(labels, dtype=np.int64),
         )
 

@@ -14,7 +14,7 @@ from typing import Iterator, Optional
 import numpy as np
 import torch
 
-from ..data.builder import EpochData
+from ..data.builder import EpochData, PackedData
 
 
 class BatchIterator:
@@ -160,3 +160,50 @@ class BatchIterator:
             pending = nxt
         if pending is not None:
             yield hand_over(*pending)
+
+
+class PackedBatchIterator:
+    """Iterates packed dict batches {'id', 'starts', 'paths', 'ends',
+    'lengths', 'label'} over a ``PackedData`` in input order.
+
+    A batch takes consecutive methods while its total rows stay within
+    ``max_batch_contexts``; a method larger than the budget forms a batch
+    on its own.  ``starts``/``paths``/``ends`` are flat int32 tensors on
+    ``device``; ``lengths`` (int64) stays on the CPU, where
+    ``forward_packed`` checks it and builds the device offsets."""
+
+    def __init__(self, data: PackedData, max_batch_contexts: int,
+                 device: Optional[torch.device] = None) -> None:
+        if max_batch_contexts < 1:
+            raise ValueError(
+                f"max_batch_contexts must be >= 1, got {max_batch_contexts}")
+        self.data = data
+        self.max_batch_contexts = int(max_batch_contexts)
+        self.device = device or torch.device("cpu")
+        # (first method, end method, first row, end row) of every batch
+        self.spans = []
+        lo = row_lo = rows = 0
+        for i, n in enumerate(data.lengths.tolist()):
+            if i > lo and rows + n > self.max_batch_contexts:
+                self.spans.append((lo, i, row_lo, row_lo + rows))
+                lo, row_lo, rows = i, row_lo + rows, 0
+            rows += n
+        if len(data.lengths) > lo:
+            self.spans.append((lo, len(data.lengths), row_lo, row_lo + rows))
+
+    def __len__(self) -> int:
+        return len(self.spans)
+
+    def __iter__(self) -> Iterator[dict]:
+        d = self.data
+        for lo, hi, r0, r1 in self.spans:
+            yield {
+                "id": torch.as_tensor(
+                    [i if i is not None else -1 for i in d.ids[lo:hi]],
+                    dtype=torch.int64),
+                "starts": torch.from_numpy(d.starts[r0:r1]).to(self.device),
+                "paths": torch.from_numpy(d.paths[r0:r1]).to(self.device),
+                "ends": torch.from_numpy(d.ends[r0:r1]).to(self.device),
+                "lengths": torch.from_numpy(d.lengths[lo:hi]),
+                "label": torch.from_numpy(d.labels[lo:hi]),
+            }

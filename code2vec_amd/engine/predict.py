@@ -11,20 +11,28 @@ names through the training reader's vocab tables exactly as
 The label tensor handed to ``forward`` is zeros: the default output head
 never reads it.  The angular-margin head does (its forward bakes the true
 label's margin into the logits), so it is rejected at construction.
+
+With ``all_contexts=True`` methods are predicted from ALL their
+path-contexts: batches are packed (``DatasetBuilder.build_packed``,
+``PackedBatchIterator``) and go through ``model.forward_packed`` (K21),
+eagerly, because their shapes vary.  Nothing is padded, subsampled or
+drawn from an RNG, and a method's code vector and attention do not depend
+on which other methods share its batch.
 """
 
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Iterator, List, Tuple
+from typing import Iterator, List, Optional, Tuple
 
 import torch
 
 from ..data.builder import DatasetBuilder
+from ..models.code2vec import ANGULAR_PREDICT_ERROR
 from ..ops import functional as Fn
 from ..ops import reference as R
 from .infer import graphed_export_forward
-from .loader import BatchIterator
+from .loader import BatchIterator, PackedBatchIterator
 
 
 @dataclass
@@ -39,15 +47,20 @@ class Prediction:
 
 
 class Predictor:
+    """``seed`` seeds the subsampling of bags larger than max_path_length
+    on the padded path; with ``all_contexts=True`` nothing is subsampled
+    and it is unused.  ``max_batch_contexts`` is the packed path's row
+    budget per batch (default ``batch_size * max_path_length``, the padded
+    path's activation footprint)."""
+
     def __init__(self, model, vocab_reader, device, topk: int = 5,
                  top_contexts: int = 5, batch_size: int = 32,
-                 use_graph: bool = True, seed: int = 123) -> None:
+                 use_graph: bool = True, seed: int = 123,
+                 all_contexts: bool = False,
+                 max_batch_contexts: Optional[int] = None) -> None:
         option = model.option
         if option.angular_margin_loss:
-            raise ValueError(
-                "Predictor does not support the angular-margin head: its "
-                "forward needs the true label, which prediction does not "
-                "have")
+            raise ValueError(ANGULAR_PREDICT_ERROR)
         for name, v in (("topk", topk), ("top_contexts", top_contexts)):
             if not 1 <= v <= R.ROW_TOPK_MAX_K:
                 raise ValueError(
@@ -56,6 +69,11 @@ class Predictor:
             raise ValueError(
                 f"topk = {topk} exceeds the model's {option.label_count} "
                 "labels")
+        if max_batch_contexts is None:
+            max_batch_contexts = batch_size * option.max_path_length
+        if max_batch_contexts < 1:
+            raise ValueError(
+                f"max_batch_contexts must be >= 1, got {max_batch_contexts}")
         self.model = model
         self.reader = vocab_reader
         self.device = torch.device(device)
@@ -64,10 +82,12 @@ class Predictor:
         self.batch_size = batch_size
         # seeds the subsampling of bags larger than max_path_length
         self.seed = seed
+        self.all_contexts = all_contexts
+        self.max_batch_contexts = max_batch_contexts
         model.eval()
         self.graphed = (
             graphed_export_forward(model, batch_size, self.device)
-            if use_graph else None
+            if use_graph and not all_contexts else None
         )
         self._builders = {}
 
@@ -81,6 +101,11 @@ class Predictor:
             return self.graphed.run(starts, paths, ends, label)
         return self.model(starts, paths, ends, label)
 
+    def _names(self, outputs):
+        """(label index, probability) tensors [B, topk] on the CPU."""
+        vals, idx, lse = Fn.row_topk(outputs.detach().contiguous(), self.topk)
+        return idx.cpu(), Fn.topk_probs(vals, lse).cpu()
+
     @torch.no_grad()
     def predict_batch(self, batch) -> List[Prediction]:
         """``batch``: a BatchIterator dict; its ``label`` is ignored."""
@@ -89,42 +114,89 @@ class Predictor:
         ends = batch["ends"].to(self.device)
         outputs, code_vector, attn = self._forward(starts, paths, ends)
 
-        vals, idx, lse = Fn.row_topk(outputs.detach().contiguous(), self.topk)
-        probs = Fn.topk_probs(vals, lse)
+        idx_c, probs_c = self._names(outputs)
         # PAD positions sort below every real context (attention >= 0), so
         # a PAD never displaces one; they are dropped on the host below
         masked = attn.detach().float().masked_fill(starts == 0, -1.0)
         kc = min(self.top_contexts, masked.shape[1])
         cvals, cidx, _ = Fn.row_topk(masked.contiguous(), kc)
 
-        idx_c, probs_c = idx.cpu(), probs.cpu()
         cvals_c, cidx_c = cvals.cpu(), cidx.cpu()
         cv_c = code_vector.detach().float().cpu()
         starts_c, paths_c, ends_c = starts.cpu(), paths.cpu(), ends.cpu()
         ids = batch["id"]
 
-        label_itos = self.reader.label_vocab.itos
-        term_itos = self.reader.terminal_vocab.itos
-        path_itos = self.reader.path_vocab.itos
         preds = []
         for i in range(starts_c.shape[0]):
-            names = [
-                (label_itos[int(idx_c[i, j])], float(probs_c[i, j]))
-                for j in range(self.topk)
-            ]
             contexts = []
             for j in range(kc):
                 c = int(cidx_c[i, j])
                 if int(starts_c[i, c]) == 0:
                     break  # only PADs follow
-                contexts.append((
-                    term_itos.get(int(starts_c[i, c]), ""),
-                    path_itos.get(int(paths_c[i, c]), ""),
-                    term_itos.get(int(ends_c[i, c]), ""),
-                    float(cvals_c[i, j]),
-                ))
-            preds.append(Prediction(int(ids[i]), names, contexts, cv_c[i]))
+                contexts.append(self._context(
+                    starts_c[i, c], paths_c[i, c], ends_c[i, c],
+                    cvals_c[i, j]))
+            preds.append(Prediction(int(ids[i]), self._name_list(
+                idx_c[i], probs_c[i]), contexts, cv_c[i]))
         return preds
+
+    @torch.no_grad()
+    def predict_packed_batch(self, batch) -> List[Prediction]:
+        """``batch``: a PackedBatchIterator dict (flat ``starts``/``paths``/
+        ``ends``, CPU ``lengths``); its ``label`` is ignored."""
+        starts = batch["starts"].to(self.device)
+        paths = batch["paths"].to(self.device)
+        ends = batch["ends"].to(self.device)
+        lens = batch["lengths"]
+        outputs, code_vector, attn = self.model.forward_packed(
+            starts, paths, ends, lens)
+
+        idx_c, probs_c = self._names(outputs)
+        # per-method top contexts in K19's order: the ragged attention
+        # goes into a [B, longest] matrix filled with -1, below every real
+        # context's weight (>= 0); PAD rows are set to -1 as well
+        B, width = lens.numel(), int(lens.max())
+        offs = torch.zeros(B, dtype=torch.int64)
+        offs[1:] = torch.cumsum(lens, 0)[:-1]
+        col = torch.arange(int(lens.sum())) - torch.repeat_interleave(
+            offs, lens)
+        flat = (torch.repeat_interleave(torch.arange(B), lens) * width
+                + col).to(self.device)
+        matrix = torch.full((B * width,), -1.0, dtype=torch.float32,
+                            device=self.device)
+        matrix[flat] = attn.detach().float().masked_fill(starts == 0, -1.0)
+        kc = min(self.top_contexts, width)
+        cvals, cidx, _ = Fn.row_topk(matrix.view(B, width), kc)
+
+        cvals_c, cidx_c = cvals.cpu(), cidx.cpu()
+        cv_c = code_vector.detach().float().cpu()
+        starts_c, paths_c, ends_c = starts.cpu(), paths.cpu(), ends.cpu()
+        ids = batch["id"]
+
+        preds = []
+        for i in range(B):
+            lo = int(offs[i])
+            contexts = []
+            for j in range(kc):
+                if float(cvals_c[i, j]) < 0.0:
+                    break  # only PADs and filler follow
+                r = lo + int(cidx_c[i, j])
+                contexts.append(self._context(
+                    starts_c[r], paths_c[r], ends_c[r], cvals_c[i, j]))
+            preds.append(Prediction(int(ids[i]), self._name_list(
+                idx_c[i], probs_c[i]), contexts, cv_c[i]))
+        return preds
+
+    def _name_list(self, idx_row, probs_row):
+        label_itos = self.reader.label_vocab.itos
+        return [(label_itos[int(idx_row[j])], float(probs_row[j]))
+                for j in range(self.topk)]
+
+    def _context(self, s, p, e, weight):
+        return (self.reader.terminal_vocab.itos.get(int(s), ""),
+                self.reader.path_vocab.itos.get(int(p), ""),
+                self.reader.terminal_vocab.itos.get(int(e), ""),
+                float(weight))
 
     def predict_items(self, items, reader=None) -> Iterator[Prediction]:
         """Predict for ``CodeItem``s in order.  ``reader`` is the reader
@@ -137,6 +209,12 @@ class Predictor:
             builder = DatasetBuilder(reader, self.model.option,
                                      split_ratio=0.0, seed=self.seed)
             self._builders[id(reader)] = builder
+        if self.all_contexts:
+            packed = builder.build_packed(list(items))
+            for batch in PackedBatchIterator(packed, self.max_batch_contexts,
+                                             device=self.device):
+                yield from self.predict_packed_batch(batch)
+            return
         data = builder.build_data(
             list(items), self.model.option.max_path_length)
         loader = BatchIterator(data, self.batch_size, shuffle=False,

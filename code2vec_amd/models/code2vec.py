@@ -69,6 +69,19 @@ def init_logical_params(option, generator: Optional[torch.Generator] = None) -> 
     return p
 
 
+ANGULAR_PREDICT_ERROR = (
+    "Predictor does not support the angular-margin head: its "
+    "forward needs the true label, which prediction does not "
+    "have")
+
+
+def _reject_packed(model) -> None:
+    """forward_packed is label-free inference: eval mode, default head."""
+    assert not model.training, "forward_packed is inference only: eval() first"
+    if model.option.angular_margin_loss:
+        raise ValueError(ANGULAR_PREDICT_ERROR)
+
+
 class Code2VecTorch(nn.Module):
     """Reference-math backend (fp32, stock torch ops) — CPU path + oracle."""
 
@@ -116,6 +129,29 @@ class Code2VecTorch(nn.Module):
         else:
             outputs = R.output_head(cv, self.output_weight, self.output_bias)
         return outputs, cv, attn
+
+    @torch.no_grad()
+    def forward_packed(self, starts, paths, ends, lengths):
+        """Code2VecHIP.forward_packed's contract on the oracle backend:
+        pads to the longest method of the batch, calls ``forward`` and
+        slices the attention back to ragged.  Returns (outputs [B, L],
+        code_vector [B, E], attention [M]).  (A method whose rows are all
+        PAD gets the padded row's uniform weights here, 1/n from K21; its
+        code vector is the same.)"""
+        _reject_packed(self)
+        M = starts.numel()
+        lens = R.check_packed_lengths(lengths, M)
+        B, C = lens.numel(), int(lens.max())
+        # row-major positions of the real contexts in the [B, C] rectangle
+        real = (torch.arange(C)[None, :] < lens[:, None]).to(starts.device)
+        padded = []
+        for t in (starts, paths, ends):
+            buf = torch.zeros(B, C, dtype=t.dtype, device=t.device)
+            buf[real] = t.reshape(-1)
+            padded.append(buf)
+        label = torch.zeros(B, dtype=torch.int64, device=starts.device)
+        outputs, cv, attn = self.forward(*padded, label)
+        return outputs, cv, attn[real]
 
     def loss(self, outputs, label, class_weight):
         return R.logsoftmax_nll(outputs, label, class_weight)
@@ -248,6 +284,33 @@ class Code2VecHIP(nn.Module):
                 outputs = Fn.OutputHead.apply(
                     cvb, self.output_weight, self.output_bias
                 )
+        return outputs, cv[:, : self.E], attn
+
+    @torch.no_grad()
+    def forward_packed(self, starts, paths, ends, lengths):
+        """Inference on a packed batch: flat [M] index tensors holding the
+        contexts of all methods back to back, and the methods' row counts
+        (list or CPU int tensor; every n >= 1, sum == M).  No pads, no cap
+        on a method's length.  Returns (outputs [B, L], code_vector
+        [B, E], attention [M]).  Gather and combiner are row-local and K21
+        is segment-local, so a method's code vector and attention do not
+        depend on the rest of the batch.  Forward only."""
+        _reject_packed(self)
+        M = starts.numel()
+        lens = R.check_packed_lengths(lengths, M)
+        starts = starts.reshape(-1).to(torch.int32).contiguous()
+        paths = paths.reshape(-1).to(torch.int32).contiguous()
+        ends = ends.reshape(-1).to(torch.int32).contiguous()
+        x = Fn.GatherConcat.apply(
+            starts.view(M, 1), paths.view(M, 1), ends.view(M, 1),
+            self.terminal_embedding, self.path_embedding, False)
+        y = Fn.CombinerLNTanh.apply(
+            x, self.input_weight, self.ln_gamma, self.ln_beta, self.E,
+            0.0, False)
+        cv, cvb, attn = Fn.attention_pool_packed(
+            y, self.attention_a, starts, lens, self.E)
+        outputs = Fn.OutputHead.apply(cvb, self.output_weight,
+                                      self.output_bias)
         return outputs, cv[:, : self.E], attn
 
     def loss(self, outputs, label, class_weight):

@@ -12,50 +12,6 @@
 
 #include "common.h"
 
-#define NINF_F (-3.4e38f)
-
-// block softmax over scores[C] (in LDS), returns nothing (scores -> attn)
-__device__ __forceinline__ void block_softmax(float* scores, float* red,
-                                              float* attn_out, int C,
-                                              long base) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wave = threadIdx.x / WAVE;
-  const int nwaves = blockDim.x / WAVE;
-  float m = NINF_F;
-  for (int c = threadIdx.x; c < C; c += blockDim.x) m = fmaxf(m, scores[c]);
-  m = wave_reduce_max(m);
-  if (lane == 0) red[wave] = m;
-  __syncthreads();
-  if (wave == 0) {
-    float v = lane < nwaves ? red[lane] : NINF_F;
-    v = wave_reduce_max(v);
-    if (lane == 0) red[0] = v;
-  }
-  __syncthreads();
-  m = red[0];
-  float ssum = 0.f;
-  for (int c = threadIdx.x; c < C; c += blockDim.x) {
-    const float e = __expf(scores[c] - m);
-    scores[c] = e;
-    ssum += e;
-  }
-  ssum = wave_reduce_sum(ssum);
-  if (lane == 0) red[8 + wave] = ssum;
-  __syncthreads();
-  if (wave == 0) {
-    float v = lane < nwaves ? red[8 + lane] : 0.f;
-    v = wave_reduce_sum(v);
-    if (lane == 0) red[8] = v;
-  }
-  __syncthreads();
-  const float inv_sum = 1.0f / red[8];
-  for (int c = threadIdx.x; c < C; c += blockDim.x) {
-    scores[c] *= inv_sum;
-    attn_out[base + c] = scores[c];
-  }
-  __syncthreads();
-}
-
 // ---------------------------------------------------------------------------
 // ts = round8(E) <= EP: only the valid columns are staged/dotted — the
 // EP-pad columns of ccv are zero and a/dcv pad is zero, so they never

@@ -1,0 +1,164 @@
+// K21 segmented attention pool over a packed (ragged) batch, forward only.
+// Math of attention_fwd_kernel (attention.hip), per method b whose rows are
+// [offsets[b], offsets[b+1]) of ccv [M, EP]:
+//   scores[c] = sum_e ccv[c,e] * a[e]            (ts = round8(E) columns)
+//   scores = scores*mask + (1-mask)*NINF          (mask = starts>0)
+//   attn = softmax(scores over the method's rows)
+//   cv[b,e] = sum_c attn[c] * ccv[c,e]            (columns [ts, EP) zero)
+//
+// One workgroup (256 threads = 4 waves) per method, the three phases of
+// attention_fwd_kernel with its mappings and summation orders: 16-lane
+// groups own one row at a time in phase 1, each wave pools a contiguous
+// quarter of the rows in phase 3, a fixed 4-way sum combines the waves.
+// Nothing is sized by the method's length n: methods of up to APK_CHUNK
+// rows keep their scores in LDS; a longer one parks its masked raw scores
+// in its own slice of the attn output, which the softmax then overwrites
+// in place (written and re-read by this block only, across
+// __syncthreads()).  Both forms run the same arithmetic in the same order,
+// so a method's bits depend on its own rows alone: not on B, its position,
+// its neighbours' lengths or the grid.  No atomics.  Rows are re-read from
+// global memory (L2) in phase 3.  Phases 1 and 3 keep several rows' loads
+// in flight (APK_ROWS, APK_PF): a long method is one block, so its time is
+// what a heavy-tailed batch waits for.
+
+#include "common.h"
+
+#define APK_CHUNK 256  // scores kept in LDS up to this many rows
+#define APK_ROWS 4     // phase 1: rows per group in flight
+#define APK_PF 8       // phase 3: rows per lane in flight
+
+// scores: LDS [APK_CHUNK] or attn + lo.  src/st/attn_seg point at the
+// method's first row.
+__device__ __forceinline__ void pool_segment(
+    const bf16* src, const int* st, const float* lds_a, float* scores,
+    float* red, float* partials, float* attn_seg, float* cv_row, bf16* cvb_row,
+    int n, int EP, int ts) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wave = threadIdx.x / WAVE;
+  const int lane16 = lane & 15;
+  const int group = (threadIdx.x >> 4);  // 16 groups of 16 lanes
+
+  // phase 1: masked scores, one row per 16-lane group; APK_ROWS rows of a
+  // group are loaded before the first is reduced (branch-free: a row past
+  // the end re-reads row n-1, in bounds, and is dropped), so a long
+  // method is not one load latency per row
+  for (int c = group; c < n; c += 16 * APK_ROWS) {
+    float s[APK_ROWS];
+#pragma unroll
+    for (int k = 0; k < APK_ROWS; ++k)
+      s[k] = group_row_dot(src + (long)min(c + 16 * k, n - 1) * EP, lds_a, ts,
+                           lane16);
+#pragma unroll
+    for (int k = 0; k < APK_ROWS; ++k) s[k] = group16_reduce_sum(s[k]);
+    if (lane16 == 0) {
+#pragma unroll
+      for (int k = 0; k < APK_ROWS; ++k) {
+        const int ck = c + 16 * k;
+        if (ck < n) {
+          const float mask = st[ck] > 0 ? 1.0f : 0.0f;
+          scores[ck] = s[k] * mask + (1.0f - mask) * NINF_F;
+        }
+      }
+    }
+  }
+  __syncthreads();
+
+  // phase 2: softmax in place, probabilities written to attn
+  block_softmax(scores, red, attn_seg, n, 0);
+
+  // phase 3: each wave pools a contiguous span of rows into per-lane
+  // column pairs, then a fixed-order sum over the four waves
+  const int span = (n + 3) / 4;
+  const int c_lo = min(n, wave * span);
+  const int c_hi = min(n, c_lo + span);
+  for (int e0 = lane * 2; e0 < EP; e0 += WAVE * 2) {
+    float acc0 = 0.f, acc1 = 0.f;
+    if (e0 < ts) {
+      // sequential in c, one FMA per element; APK_PF rows are in flight at
+      // a time (raw bf16 pairs: bf16 -> f32 is the bit pattern moved to the
+      // high half), the order of the sum does not change
+      const bf16* col = src + e0;
+      int c = c_lo;
+      for (; c + APK_PF <= c_hi; c += APK_PF) {
+        unsigned r[APK_PF];
+        float at[APK_PF];
+#pragma unroll
+        for (int k = 0; k < APK_PF; ++k)
+          r[k] = *(const unsigned*)(col + (long)(c + k) * EP);
+#pragma unroll
+        for (int k = 0; k < APK_PF; ++k) at[k] = scores[c + k];
+#pragma unroll
+        for (int k = 0; k < APK_PF; ++k) {
+          acc0 = __builtin_fmaf(at[k], __uint_as_float(r[k] << 16), acc0);
+          acc1 = __builtin_fmaf(at[k], __uint_as_float(r[k] & 0xffff0000u),
+                                acc1);
+        }
+      }
+      for (; c < c_hi; ++c) {
+        const unsigned r = *(const unsigned*)(col + (long)c * EP);
+        const float at = scores[c];
+        acc0 = __builtin_fmaf(at, __uint_as_float(r << 16), acc0);
+        acc1 = __builtin_fmaf(at, __uint_as_float(r & 0xffff0000u), acc1);
+      }
+    }
+    partials[wave * EP + e0] = acc0;
+    partials[wave * EP + e0 + 1] = acc1;
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < EP; e += blockDim.x) {
+    const float s = partials[e] + partials[EP + e] + partials[2 * EP + e] +
+                    partials[3 * EP + e];
+    cv_row[e] = s;
+    cvb_row[e] = f2bf(s);
+  }
+}
+
+// attn is read back by the block that wrote it: no __restrict__ on it
+__global__ __launch_bounds__(256) void attention_packed_fwd_kernel(
+    const bf16* __restrict__ ccv, const float* __restrict__ a,
+    const int* __restrict__ starts, const int* __restrict__ offsets,
+    float* __restrict__ cv, bf16* __restrict__ cvb, float* attn, long M,
+    int EP, int ts) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  // layout: [a f32 EP] [scores APK_CHUNK] [red 64] [partials 4*EP]
+  float* lds_a = (float*)smem;
+  float* lds_scores = lds_a + EP;
+  float* red = lds_scores + APK_CHUNK;
+  float* partials = red + 64;
+
+  const long b = blockIdx.x;
+  // offsets are built by the host wrapper (0 = o[0] < o[1] < ... = M); the
+  // clamp only keeps a caller's mistake inside the buffers
+  const long lo = max(0L, min((long)offsets[b], M));
+  const long hi = max(lo, min((long)offsets[b + 1], M));
+  const int n = (int)(hi - lo);
+
+  for (int e = threadIdx.x; e < EP; e += blockDim.x) lds_a[e] = a[e];
+  __syncthreads();
+
+  const bf16* src = ccv + lo * EP;  // 64-bit row addressing
+  if (n <= APK_CHUNK)
+    pool_segment(src, starts + lo, lds_a, lds_scores, red, partials,
+                 attn + lo, cv + b * EP, cvb + b * EP, n, EP, ts);
+  else
+    pool_segment(src, starts + lo, lds_a, attn + lo, red, partials,
+                 attn + lo, cv + b * EP, cvb + b * EP, n, EP, ts);
+}
+
+extern "C" {
+
+int attention_packed_chunk() { return APK_CHUNK; }
+
+void launch_attention_packed_fwd(const void* ccv, const float* a,
+                                 const int* starts, const int* offsets,
+                                 float* cv, void* cvb, float* attn, long M,
+                                 long B, int EP, int E, hipStream_t stream) {
+  if (B < 1) return;
+  int ts = (E + 7) & ~7;
+  if (ts > EP) ts = EP;
+  const size_t smem = ((size_t)EP + APK_CHUNK + 64 + 4 * (size_t)EP) * 4;
+  attention_packed_fwd_kernel<<<(unsigned)B, 256, smem, stream>>>(
+      (const bf16*)ccv, a, starts, offsets, cv, (bf16*)cvb, attn, M, EP, ts);
+}
+
+}  // extern "C"

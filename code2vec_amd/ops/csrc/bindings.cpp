@@ -91,6 +91,10 @@ void launch_attention_bwd_compact_reg(const void*, int, const float*,
                                       const void*, const int*, const float*,
                                       float*, float*, int, int, int, int, int,
                                       hipStream_t);
+int attention_packed_chunk();
+void launch_attention_packed_fwd(const void*, const float*, const int*,
+                                 const int*, float*, void*, float*, long, long,
+                                 int, int, hipStream_t);
 void launch_slab_sum2_f32(const float*, const float*, float*, float*, int,
                           int, hipStream_t);
 void launch_loss_reduce(const float*, float*, float*, int, hipStream_t);
@@ -514,6 +518,44 @@ void attention_bwd_compact_reg(torch::Tensor dcv, torch::Tensor dattn,
       starts.data_ptr<int>(), attn.data_ptr<float>(), ds.data_ptr<float>(),
       da.data_ptr<float>(), B, C, EP, (int)E, has_dattn ? 1 : 0,
       cur_stream());
+}
+
+// K21 segmented attention pool over a packed batch: ccv [M, EP] bf16,
+// starts [M] i32, offsets [B+1] i32 on the device (method b owns rows
+// [offsets[b], offsets[b+1])); writes cv [B, EP] f32, cvb [B, EP] bf16 and
+// attn [M] f32.  The kernel trusts offsets: functional.attention_pool_packed
+// derives them from host-checked lengths and is the only caller.
+void attention_pool_packed(torch::Tensor ccv, torch::Tensor a,
+                           torch::Tensor starts, torch::Tensor offsets,
+                           torch::Tensor cv, torch::Tensor cvb,
+                           torch::Tensor attn, int64_t E, int64_t chunk) {
+  CHK_CUDA(ccv); CHK_CONTIG(ccv); CHK_DT(ccv, torch::kBFloat16);
+  CHK_CUDA(a); CHK_CONTIG(a); CHK_DT(a, torch::kFloat32);
+  CHK_CUDA(starts); CHK_CONTIG(starts); CHK_DT(starts, torch::kInt32);
+  CHK_CUDA(offsets); CHK_CONTIG(offsets); CHK_DT(offsets, torch::kInt32);
+  CHK_CUDA(cv); CHK_CONTIG(cv); CHK_DT(cv, torch::kFloat32);
+  CHK_CUDA(cvb); CHK_CONTIG(cvb); CHK_DT(cvb, torch::kBFloat16);
+  CHK_CUDA(attn); CHK_CONTIG(attn); CHK_DT(attn, torch::kFloat32);
+  TORCH_CHECK(ccv.dim() == 2, "ccv must be [M, EP]");
+  TORCH_CHECK(chunk == attention_packed_chunk(),
+              "attention_pool_packed: score chunk differs from the compiled ",
+              attention_packed_chunk());
+  const long M = ccv.size(0);
+  const int EP = ccv.size(1);
+  const long B = offsets.numel() - 1;
+  TORCH_CHECK(EP % 32 == 0 && EP >= 32 && EP <= 1024 && E >= 1 && E <= EP,
+              "attention_pool_packed: EP must be a multiple of 32 in "
+              "32..1024 and 1 <= E <= EP");
+  TORCH_CHECK(B >= 1 && B <= M && M < (1L << 31) && a.numel() == EP &&
+              starts.numel() == M && attn.numel() == M &&
+              cv.numel() == B * EP && cvb.numel() == B * EP,
+              "attention_pool_packed shapes");
+  TORCH_CHECK((uintptr_t)ccv.data_ptr() % 16 == 0, "ccv must be 16-B aligned");
+  launch_attention_packed_fwd(ccv.data_ptr(), a.data_ptr<float>(),
+                              starts.data_ptr<int>(), offsets.data_ptr<int>(),
+                              cv.data_ptr<float>(), cvb.data_ptr(),
+                              attn.data_ptr<float>(), M, B, EP, (int)E,
+                              cur_stream());
 }
 
 // combiner backward that rebuilds dout = bf16(attn*dcv + ds*a) in
@@ -1567,6 +1609,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attention_stream_ok", &attention_stream_ok);
   m.def("attention_fwd_scores", &attention_fwd_scores);
   m.def("attention_bwd_compact_reg", &attention_bwd_compact_reg);
+  m.def("attention_pool_packed", &attention_pool_packed);
   m.def("combiner_bwd_recompute", &combiner_bwd_recompute);
   m.def("slab_sum2_f32", &slab_sum2_f32);
   m.def("loss_reduce", &loss_reduce);

@@ -104,6 +104,55 @@ __device__ __forceinline__ float group_row_dot(const bf16* row,
   return s;
 }
 
+// masked-score fill of the attention pools (reference NINF)
+#define NINF_F (-3.4e38f)
+
+// Block softmax over scores[C], in place (scores -> attn probabilities),
+// also written to attn_out[base + c].  Shared by attention.hip and
+// attention_packed.hip.  A thread touches only the entries c = tid + k *
+// blockDim.x in every pass, so ``scores`` may be LDS or the block's own
+// slice of attn_out (scores == attn_out + base).  red: >= 16 floats of LDS.
+__device__ __forceinline__ void block_softmax(float* scores, float* red,
+                                              float* attn_out, int C,
+                                              long base) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wave = threadIdx.x / WAVE;
+  const int nwaves = blockDim.x / WAVE;
+  float m = NINF_F;
+  for (int c = threadIdx.x; c < C; c += blockDim.x) m = fmaxf(m, scores[c]);
+  m = wave_reduce_max(m);
+  if (lane == 0) red[wave] = m;
+  __syncthreads();
+  if (wave == 0) {
+    float v = lane < nwaves ? red[lane] : NINF_F;
+    v = wave_reduce_max(v);
+    if (lane == 0) red[0] = v;
+  }
+  __syncthreads();
+  m = red[0];
+  float ssum = 0.f;
+  for (int c = threadIdx.x; c < C; c += blockDim.x) {
+    const float e = __expf(scores[c] - m);
+    scores[c] = e;
+    ssum += e;
+  }
+  ssum = wave_reduce_sum(ssum);
+  if (lane == 0) red[8 + wave] = ssum;
+  __syncthreads();
+  if (wave == 0) {
+    float v = lane < nwaves ? red[8 + lane] : 0.f;
+    v = wave_reduce_sum(v);
+    if (lane == 0) red[8] = v;
+  }
+  __syncthreads();
+  const float inv_sum = 1.0f / red[8];
+  for (int c = threadIdx.x; c < C; c += blockDim.x) {
+    scores[c] *= inv_sum;
+    attn_out[base + c] = scores[c];
+  }
+  __syncthreads();
+}
+
 // fp32 atomic add using the native global_atomic_add_f32 (no CAS loop).
 __device__ __forceinline__ void atomic_add_f32(float* p, float v) {
   unsafeAtomicAdd(p, v);

@@ -870,6 +870,56 @@ class AttentionPool(torch.autograd.Function):
         return dccv, _slab_sum(da_p), None, None
 
 
+# rows up to which K21 keeps a method's scores in LDS (longer methods park
+# them in their attn slice); the extension checks it against the compiled
+# value.  Exposed so tests can plant lengths on the boundary.
+ATTN_PACKED_CHUNK = 256
+
+
+def attention_pool_packed(ccv: torch.Tensor, a: torch.Tensor,
+                          starts: torch.Tensor, lengths, E: int, out=None):
+    """K21: masked attention pool over a packed batch, forward only.
+
+    ccv: bf16 [M, EP], the rows of all methods back to back; a: f32 [EP];
+    starts: i32 [M] (mask = starts > 0); lengths: the methods' row counts
+    as a list or a CPU int32/int64 tensor.  They are checked here on the
+    host (every n >= 1, sum == M; ValueError before anything is launched)
+    and the device offsets the kernel trusts are built from them here and
+    nowhere else.  Returns (cv f32 [B, EP], cvb bf16 [B, EP], attn f32
+    [M]).  A method's result depends on its own rows only, bit for bit.
+    ``out`` = (cv, cvb, attn) writes into the caller's buffers (the
+    binding checks them).  CPU tensors take
+    ops/reference.py::attention_pool_packed."""
+    from . import reference as R
+
+    if ccv.dim() != 2:
+        raise ValueError(
+            f"attention_pool_packed: ccv must be [M, EP], got "
+            f"{tuple(ccv.shape)}")
+    M, EP = ccv.shape
+    lens = R.check_packed_lengths(lengths, M)
+    if starts.numel() != M:
+        raise ValueError(
+            f"attention_pool_packed: starts has {starts.numel()} entries "
+            f"for {M} rows")
+    if not ccv.is_cuda:
+        return R.attention_pool_packed(ccv, a, starts, lens, E)
+    B = lens.numel()
+    dev = ccv.device
+    offsets = torch.zeros(B + 1, dtype=torch.int32)
+    offsets[1:] = torch.cumsum(lens, 0)
+    offsets = offsets.to(dev)
+    if out is not None:
+        cv, cvb, attn = out
+    else:
+        cv = torch.empty(B, EP, dtype=torch.float32, device=dev)
+        cvb = torch.empty(B, EP, dtype=torch.bfloat16, device=dev)
+        attn = torch.empty(M, dtype=torch.float32, device=dev)
+    ext().attention_pool_packed(ccv, a, starts.reshape(-1), offsets, cv, cvb,
+                                attn, int(E), ATTN_PACKED_CHUNK)
+    return cv, cvb, attn
+
+
 class CombinerAttentionPool(torch.autograd.Function):
     """K3-K9 as one autograd node (EP = 128): combiner_fwd, then
     attention_fwd, returning cv (f32), attn and cv rounded to bf16 (what

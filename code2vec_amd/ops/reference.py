@@ -178,3 +178,56 @@ def logsoftmax_nll(logits, label, weight):
     """
     logp = F.log_softmax(logits.float(), dim=1)
     return F.nll_loss(logp, label.long(), weight=weight)
+
+
+def check_packed_lengths(lengths, M: int):
+    """Host-side contract of a packed batch's lengths (list or CPU
+    int32/int64 tensor): at least one method, every n >= 1, sum == M.
+    Returns them as a CPU int64 tensor."""
+    if isinstance(lengths, torch.Tensor):
+        if lengths.is_cuda or lengths.dtype not in (torch.int32, torch.int64):
+            raise ValueError(
+                "packed lengths must be a CPU int32/int64 tensor or a list")
+        lens = lengths.detach().to(torch.int64).reshape(-1)
+    else:
+        lens = torch.tensor([int(n) for n in lengths], dtype=torch.int64)
+    if lens.numel() < 1:
+        raise ValueError("packed lengths: no methods")
+    if int(lens.min()) < 1:
+        raise ValueError(
+            f"packed lengths: every method needs n >= 1 rows, got "
+            f"{int(lens.min())}")
+    total = int(lens.sum())
+    if total != int(M):
+        raise ValueError(
+            f"packed lengths sum to {total}, the batch has {int(M)} rows")
+    if total >= 1 << 31:
+        raise ValueError("packed batch: M must be < 2^31")
+    return lens
+
+
+def attention_pool_packed(ccv, a, starts, lengths, E: int):
+    """K21: attention pool over a packed batch, a loop over segments in
+    fp32.
+
+    ccv: [M, EP] rows of all methods back to back; a: [EP]; starts: [M]
+    (mask = starts > 0); lengths: host list / CPU int tensor, method b owns
+    the next lengths[b] rows.  Softmax over each method's own rows, pool
+    over the round8(E) valid columns, columns past them zero.  Returns
+    (cv f32 [B, EP], cvb bf16 [B, EP], attn f32 [M])."""
+    M, EP = ccv.shape
+    lens = check_packed_lengths(lengths, M)
+    ts = min((int(E) + 7) & ~7, EP)
+    c32 = ccv.float()
+    a32 = a.float()
+    mask = (starts.reshape(-1) > 0).float()
+    cv = torch.zeros(lens.numel(), EP, dtype=torch.float32, device=ccv.device)
+    attn = torch.empty(M, dtype=torch.float32, device=ccv.device)
+    lo = 0
+    for b, n in enumerate(lens.tolist()):
+        seg = c32[lo:lo + n, :ts].unsqueeze(0)
+        at = attention(seg, a32[:ts], mask[lo:lo + n].unsqueeze(0))
+        cv[b, :ts] = code_vector(seg, at)[0]
+        attn[lo:lo + n] = at[0]
+        lo += n
+    return cv, cv.to(torch.bfloat16), attn

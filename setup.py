@@ -18,6 +18,7 @@ SRC = [
     "code2vec_amd/ops/csrc/gather_concat.hip",
     "code2vec_amd/ops/csrc/combiner.hip",
     "code2vec_amd/ops/csrc/attention.hip",
+    "code2vec_amd/ops/csrc/attention_packed.hip",
     "code2vec_amd/ops/csrc/logsoftmax_nll.hip",
     "code2vec_amd/ops/csrc/adam.hip",
     "code2vec_amd/ops/csrc/index_group.hip",

@@ -14,6 +14,11 @@ files.  Its labels may be names the model never saw; they only appear as
 the "expected" string (normalized like the training labels, so it can be
 compared with a predicted name).
 
+By default a method goes through the training layout: padded to
+--max_path_length contexts, a longer one subsampled (seeded by
+--random_seed).  --all_contexts predicts from every context of every
+method instead (packed batches, no padding, no subsampling, no seed).
+
     python tools/predict.py --model output/code2vec.model \\
         --corpus_path dataset/corpus.txt \\
         --path_idx_path dataset/path_idxs.txt \\
@@ -62,7 +67,17 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--batch_size", type=int, default=32)
     p.add_argument("--random_seed", type=int, default=123,
                    help="seeds the context subsampling of methods with more "
-                        "than --max_path_length contexts")
+                        "than --max_path_length contexts (unused with "
+                        "--all_contexts)")
+    p.add_argument("--all_contexts", action="store_true", default=False,
+                   help="predict from ALL of a method's contexts (packed "
+                        "variable-length batches): no padding, no "
+                        "subsampling, one answer per method whatever the "
+                        "seed and the batch")
+    p.add_argument("--max_batch_contexts", type=int, default=None,
+                   help="with --all_contexts: path-contexts per batch "
+                        "(default: batch_size * max_path_length); a larger "
+                        "method runs alone")
     # model shape: main.py's names and defaults
     p.add_argument("--terminal_embed_size", type=int, default=100)
     p.add_argument("--path_embed_size", type=int, default=100)
@@ -116,6 +131,8 @@ def main(argv=None) -> int:
         v = getattr(args, flag)
         if not 1 <= v <= MAX_K:
             parser.error(f"--{flag} must be in 1..{MAX_K}, got {v}")
+    if args.max_batch_contexts is not None and args.max_batch_contexts < 1:
+        parser.error("--max_batch_contexts must be >= 1")
 
     import torch
 
@@ -162,7 +179,9 @@ def main(argv=None) -> int:
         predictor = Predictor(model, reader, device, topk=args.topk,
                               top_contexts=args.top_contexts,
                               batch_size=args.batch_size,
-                              seed=args.random_seed)
+                              seed=args.random_seed,
+                              all_contexts=args.all_contexts,
+                              max_batch_contexts=args.max_batch_contexts)
     except ValueError as e:
         raise SystemExit(f"predict: {e}") from e
 
