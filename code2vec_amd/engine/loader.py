@@ -17,8 +17,27 @@ import torch
 from ..data.builder import EpochData, PackedData
 
 
+def stripped_lengths(starts: np.ndarray) -> np.ndarray:
+    """Row count of every method of a padded [N, C] ``starts`` array once
+    its trailing pads are stripped: the position of the last ``starts > 0``
+    plus one, at least 1 (an all-pad row keeps one PAD context)."""
+    real = starts > 0
+    C = starts.shape[1]
+    last = C - np.argmax(real[:, ::-1], axis=1)
+    return np.where(real.any(axis=1), last, 1).astype(np.int64)
+
+
 class BatchIterator:
-    """Iterates dict batches {'id','starts','paths','ends','label'}."""
+    """Iterates dict batches {'id','starts','paths','ends','label'}.
+
+    ``pack=True`` (training on packed batches) yields the same methods in
+    the same order — same seed, same permutation, same sampled contexts —
+    with each method's trailing pads stripped: ``starts``/``paths``/``ends``
+    are flat int32 [M] tensors holding the methods' rows back to back,
+    ``lengths`` (int64 [B]) stays on the CPU, and on the GPU ``offsets``
+    (int32 [B+1], the exclusive prefix sum of ``lengths``) arrives with the
+    batch.  A batch never has more than ``row_capacity`` = batch_size * C
+    rows."""
 
     def __init__(
         self,
@@ -28,8 +47,13 @@ class BatchIterator:
         seed: int = 0,
         device: Optional[torch.device] = None,
         prefetch: bool = True,
+        pack: bool = False,
     ) -> None:
         self.data = data
+        self.pack = bool(pack)
+        self.row_capacity = batch_size * int(data.starts.shape[1])
+        # once per epoch (an iterator serves one epoch's data), in numpy
+        self.lengths = stripped_lengths(data.starts) if self.pack else None
         self.batch_size = batch_size
         self.shuffle = shuffle
         self.seed = seed
@@ -54,19 +78,27 @@ class BatchIterator:
             # per-slot event keeps the host from overwriting a slot whose
             # copy is still in flight.
             C = self.starts.shape[1]
+            # packed batches are staged flat, at capacity (batch_size * C
+            # rows), plus their offsets
+            rows = (batch_size * C,) if self.pack else (batch_size, C)
             self._stage = [
                 {
-                    "starts": torch.empty(batch_size, C, dtype=torch.int32,
+                    "starts": torch.empty(*rows, dtype=torch.int32,
                                           pin_memory=True),
-                    "paths": torch.empty(batch_size, C, dtype=torch.int32,
+                    "paths": torch.empty(*rows, dtype=torch.int32,
                                          pin_memory=True),
-                    "ends": torch.empty(batch_size, C, dtype=torch.int32,
+                    "ends": torch.empty(*rows, dtype=torch.int32,
                                         pin_memory=True),
                     "label": torch.empty(batch_size, dtype=torch.int64,
                                          pin_memory=True),
                 }
                 for _ in range(2)
             ]
+            if self.pack:
+                for st in self._stage:
+                    st["offsets"] = torch.empty(batch_size + 1,
+                                                dtype=torch.int32,
+                                                pin_memory=True)
             self._stage_ev = [torch.cuda.Event(), torch.cuda.Event()]
             self._stage_used = [False, False]
 
@@ -89,6 +121,18 @@ class BatchIterator:
 
         def host_batch(lo: int, hi: int) -> dict:
             idx = order[lo:hi]
+            if self.pack:
+                lens = torch.from_numpy(self.lengths[idx.numpy()])
+                C = self.starts.shape[1]
+                real = torch.arange(C)[None, :] < lens[:, None]
+                return {
+                    "id": self.ids[idx],
+                    "starts": self.starts[idx][real],
+                    "paths": self.paths[idx][real],
+                    "ends": self.ends[idx][real],
+                    "lengths": lens,
+                    "label": self.labels[idx],
+                }
             return {
                 "id": self.ids[idx],
                 "starts": self.starts[idx],
@@ -117,7 +161,47 @@ class BatchIterator:
             {k: v.numpy() for k, v in s.items()} for s in self._stage
         ]
 
+        if self.pack:
+            C = self.starts.shape[1]
+            rect = np.empty((bs, C), dtype=np.int32)  # one field's rectangle
+            cols = np.arange(C)[None, :]
+
+        def stage_and_copy_packed(slot: int, lo: int, hi: int):
+            if self._stage_used[slot]:
+                self._stage_ev[slot].synchronize()  # copy out of this slot done
+            self._stage_used[slot] = True
+            idx = order[lo:hi]
+            idx_np = order_np[lo:hi]
+            k = hi - lo
+            st = self._stage[slot]
+            sn = stage_np[slot]
+            lens = self.lengths[idx_np]
+            m = int(lens.sum())
+            real = (cols < lens[:, None]).ravel()
+            for key in ("starts", "paths", "ends"):
+                np.take(src_np[key], idx_np, axis=0, out=rect[:k])
+                np.compress(real, rect[:k].ravel(), out=sn[key][:m])
+            np.take(src_np["label"], idx_np, axis=0, out=sn["label"][:k])
+            sn["offsets"][0] = 0
+            np.cumsum(lens, out=sn["offsets"][1:k + 1])
+            ev = self._stage_ev[slot]
+            with torch.cuda.stream(self._copy_stream):
+                db = {
+                    "id": self.ids[idx],
+                    "starts": st["starts"][:m].to(self.device, non_blocking=True),
+                    "paths": st["paths"][:m].to(self.device, non_blocking=True),
+                    "ends": st["ends"][:m].to(self.device, non_blocking=True),
+                    "offsets": st["offsets"][:k + 1].to(self.device,
+                                                        non_blocking=True),
+                    "lengths": torch.from_numpy(lens),
+                    "label": st["label"][:k].to(self.device, non_blocking=True),
+                }
+                ev.record(self._copy_stream)
+            return db, ev
+
         def stage_and_copy(slot: int, lo: int, hi: int):
+            if self.pack:
+                return stage_and_copy_packed(slot, lo, hi)
             if self._stage_used[slot]:
                 self._stage_ev[slot].synchronize()  # copy out of this slot done
             self._stage_used[slot] = True
@@ -148,7 +232,7 @@ class BatchIterator:
             cur = torch.cuda.current_stream(self.device)
             cur.wait_event(ev)
             for k, v in db.items():
-                if k != "id":
+                if v.is_cuda:  # "id" (and a packed batch's lengths) are host
                     v.record_stream(cur)
             return db
 

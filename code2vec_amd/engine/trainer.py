@@ -63,6 +63,9 @@ class TrainerConfig:
         self.random_seed = args.random_seed
         self.batch_size = args.batch_size
         self.no_artifact_export = getattr(args, "no_artifact_export", False)
+        # train on packed batches (trailing pads stripped, no pad rows);
+        # evaluation and export stay padded
+        self.pack_batches = bool(getattr(args, "pack_batches", False))
 
 
 class Trainer:
@@ -84,6 +87,13 @@ class Trainer:
         self.ctx = ctx
         self.trial = trial
         self.device = ctx.device
+        self.pack_batches = bool(getattr(config, "pack_batches", False))
+        if self.pack_batches and ctx.world_size > 1:
+            raise ValueError(
+                "--pack_batches supports single-process training only "
+                f"(world_size is {ctx.world_size}): packed batches differ in "
+                "row count between ranks, which the data-parallel step does "
+                "not handle")
 
         # loss class weights = 1/label_freq (reference main.py:129-130)
         freq = torch.tensor(
@@ -245,7 +255,8 @@ class Trainer:
 
     # ------------------------------------------------------------------
     def _make_loader(self, train: bool, epoch: int,
-                     keep_pending: bool = False) -> BatchIterator:
+                     keep_pending: bool = False,
+                     pack: bool = False) -> BatchIterator:
         if train:
             pending = self._next_train
             if pending is not None and pending[0] == epoch:
@@ -270,10 +281,16 @@ class Trainer:
             shuffle=True,
             seed=self.cfg.random_seed + (0 if train else 104729) + epoch,
             device=self.device,
+            pack=pack,
         )
 
     def _train_epoch(self, epoch: int):
-        loader = self._make_loader(train=True, epoch=epoch)
+        """One epoch; returns (summed loss, contexts processed).  With
+        ``pack_batches`` the count is REAL rows (pads stripped), so
+        path_contexts_per_sec is not comparable with a padded run's, which
+        counts batch_size * max_path_length per step."""
+        pack = self.pack_batches
+        loader = self._make_loader(train=True, epoch=epoch, pack=pack)
         # kick off next epoch's rebuild in the background.  NOTE: the
         # builder's pinned pool is double-buffered per (tag, parity) so the
         # background build never overwrites the epoch currently training.
@@ -296,7 +313,19 @@ class Trainer:
 
             self.ddp.zero_grad()
             self.roctx.push("forward")
-            outputs, _, _ = model(starts, paths, ends, label)
+            if pack:
+                if isinstance(model, Code2VecHIP):
+                    offsets = batch.get("offsets")
+                    outputs, _, _ = model.forward_packed_train(
+                        starts, paths, ends, batch["lengths"], label,
+                        offsets=(offsets.to(self.device)
+                                 if offsets is not None else None),
+                        row_capacity=loader.row_capacity)
+                else:
+                    outputs, _, _ = model.forward_packed_train(
+                        starts, paths, ends, batch["lengths"], label)
+            else:
+                outputs, _, _ = model(starts, paths, ends, label)
             loss = model.loss(outputs, label, self.class_weight)
             self.roctx.pop()
             self.roctx.push("backward")

@@ -153,6 +153,23 @@ class Code2VecTorch(nn.Module):
         outputs, cv, attn = self.forward(*padded, label)
         return outputs, cv, attn[real]
 
+    def forward_packed_train(self, starts, paths, ends, lengths, label):
+        """Code2VecHIP.forward_packed_train's contract on the oracle
+        backend, with autograd on: pads to the longest method of the batch
+        and calls ``forward``.  Returns (outputs [B, L], code_vector
+        [B, E], attention [M])."""
+        M = starts.numel()
+        lens = R.check_packed_lengths(lengths, M)
+        B, C = lens.numel(), int(lens.max())
+        real = (torch.arange(C)[None, :] < lens[:, None]).to(starts.device)
+        padded = []
+        for t in (starts, paths, ends):
+            buf = torch.zeros(B, C, dtype=t.dtype, device=t.device)
+            buf[real] = t.reshape(-1)
+            padded.append(buf)
+        outputs, cv, attn = self.forward(*padded, label)
+        return outputs, cv, attn[real]
+
     def loss(self, outputs, label, class_weight):
         return R.logsoftmax_nll(outputs, label, class_weight)
 
@@ -261,6 +278,14 @@ class Code2VecHIP(nn.Module):
             cv, attn = Fn.AttentionPool.apply(ccv, self.attention_a, starts,
                                               self.E)
             cvb = cv.to(torch.bfloat16)
+        outputs = self._head(cvb, label)
+        return outputs, cv[:, : self.E], attn
+
+    def _head(self, cvb, label):
+        """The output head over cvb [B, EP] bf16 (padded and packed
+        training share it: the heads see the code vectors and the label
+        only)."""
+        opt = self.option
         if opt.angular_margin_loss:
             outputs = Fn.angular_margin_head_hip(
                 cvb, self.output_weight, label,
@@ -284,6 +309,48 @@ class Code2VecHIP(nn.Module):
                 outputs = Fn.OutputHead.apply(
                     cvb, self.output_weight, self.output_bias
                 )
+        return outputs
+
+    def forward_packed_train(self, starts, paths, ends, lengths, label,
+                             offsets=None, row_capacity=None):
+        """Training forward on a packed batch (autograd on): flat [M] index
+        tensors holding the methods' contexts back to back and the
+        methods' row counts (list or CPU int tensor; every n >= 1, sum ==
+        M, checked on the host before any launch).  No pad row is
+        gathered, combined, scored or back-propagated.  Returns (outputs
+        [B, L], code_vector [B, E], attention [M]); ``loss`` and
+        ``backward`` follow as after ``forward``.
+
+        ``offsets``: device int32 [B+1] offsets a loader built from these
+        same lengths (saves the host-to-device copy here).
+        ``row_capacity``: the most rows any batch of the run will have
+        (batch_size * max_path_length); the row-sized persistent scratch of
+        the table-gradient grouping is then allocated once for that many
+        rows instead of once per distinct M."""
+        M = starts.numel()
+        starts = starts.reshape(-1).to(torch.int32).contiguous()
+        paths = paths.reshape(-1).to(torch.int32).contiguous()
+        ends = ends.reshape(-1).to(torch.int32).contiguous()
+        lens, offsets = Fn.packed_offsets(lengths, M, starts.device, offsets)
+        if not (paths.numel() == M and ends.numel() == M):
+            raise ValueError("packed starts/paths/ends sizes differ")
+        x = Fn.GatherConcat.apply(
+            starts.view(M, 1), paths.view(M, 1), ends.view(M, 1),
+            self.terminal_embedding, self.path_embedding, True,
+            row_capacity)
+        if Fn.combiner_attention_pool_supported(x, self.input_weight):
+            cv, attn, cvb = Fn.combiner_attention_pool_packed(
+                x, self.input_weight, self.ln_gamma, self.ln_beta,
+                self.attention_a, starts, lens, self.E, self.dropout_p,
+                self.training, offsets=offsets)
+        else:
+            y = Fn.CombinerLNTanh.apply(
+                x, self.input_weight, self.ln_gamma, self.ln_beta,
+                self.E, self.dropout_p, self.training)
+            cv, attn = Fn.attention_pool_packed_train(
+                y, self.attention_a, starts, lens, self.E, offsets=offsets)
+            cvb = cv.to(torch.bfloat16)
+        outputs = self._head(cvb, label)
         return outputs, cv[:, : self.E], attn
 
     @torch.no_grad()

@@ -95,6 +95,14 @@ int attention_packed_chunk();
 void launch_attention_packed_fwd(const void*, const float*, const int*,
                                  const int*, float*, void*, float*, long, long,
                                  int, int, hipStream_t);
+void launch_attention_packed_bwd(const void*, int, const float*, const void*,
+                                 const float*, const int*, const int*,
+                                 const float*, void*, float*, int*, float*,
+                                 long, long, int, int, hipStream_t);
+void launch_combiner_bwd_recompute_packed(
+    const float*, const float*, const void*, int, const float*, const int*,
+    long, const void*, const void*, const float*, const float*, const float*,
+    const float*, void*, float*, float*, long, int, float, hipStream_t);
 void launch_slab_sum2_f32(const float*, const float*, float*, float*, int,
                           int, hipStream_t);
 void launch_loss_reduce(const float*, float*, float*, int, hipStream_t);
@@ -597,6 +605,138 @@ void combiner_bwd_recompute(torch::Tensor attn, torch::Tensor ds,
       gamma.data_ptr<float>(), beta.data_ptr<float>(), dz.data_ptr(),
       dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), M, (int)E, (float)p,
       cur_stream());
+}
+
+// K22 segmented attention backward over a packed batch (the backward of
+// attention_pool_packed): dcv [B, EP] f32 or bf16, ccv [M, EP] bf16, starts /
+// attn [M], offsets [B+1] i32 on the device, dattn [M] f32 or empty.
+// Compact form (dccv undefined/empty): writes ds [M] f32, seg [M] i32 (row ->
+// method) and da_p [B, EP].  Dense form: writes dccv [M, EP] bf16 and da_p;
+// ds [M] is its workspace.  As in the forward, the kernel trusts offsets.
+static void attention_packed_bwd_impl(
+    torch::Tensor dcv, torch::Tensor dattn, torch::Tensor ccv, torch::Tensor a,
+    torch::Tensor starts, torch::Tensor offsets, torch::Tensor attn,
+    torch::Tensor* dccv, torch::Tensor ds, torch::Tensor* seg,
+    torch::Tensor da, int64_t E, bool has_dattn, int64_t chunk) {
+  CHK_CUDA(dcv); CHK_CONTIG(dcv);
+  const bool dcv_bf16 = dcv.scalar_type() == torch::kBFloat16;
+  TORCH_CHECK(dcv_bf16 || dcv.scalar_type() == torch::kFloat32,
+              "dcv must be f32 or bf16");
+  CHK_CUDA(ccv); CHK_CONTIG(ccv); CHK_DT(ccv, torch::kBFloat16);
+  CHK_CUDA(a); CHK_CONTIG(a); CHK_DT(a, torch::kFloat32);
+  CHK_CUDA(starts); CHK_CONTIG(starts); CHK_DT(starts, torch::kInt32);
+  CHK_CUDA(offsets); CHK_CONTIG(offsets); CHK_DT(offsets, torch::kInt32);
+  CHK_CUDA(attn); CHK_CONTIG(attn); CHK_DT(attn, torch::kFloat32);
+  CHK_CUDA(ds); CHK_CONTIG(ds); CHK_DT(ds, torch::kFloat32);
+  CHK_CUDA(da); CHK_CONTIG(da); CHK_DT(da, torch::kFloat32);
+  TORCH_CHECK(ccv.dim() == 2, "ccv must be [M, EP]");
+  TORCH_CHECK(dcv.dim() == 2, "dcv must be [B, EP]");
+  TORCH_CHECK(chunk == attention_packed_chunk(),
+              "attention_packed_bwd: score chunk differs from the compiled ",
+              attention_packed_chunk());
+  const long M = ccv.size(0);
+  const int EP = ccv.size(1);
+  const long B = dcv.size(0);
+  TORCH_CHECK(EP % 32 == 0 && EP >= 32 && EP <= 384 && E >= 1 && E <= EP,
+              "attention_packed_bwd: EP must be a multiple of 32 in 32..384 "
+              "and 1 <= E <= EP");
+  TORCH_CHECK(offsets.numel() == B + 1,
+              "attention_packed_bwd: offsets must have B + 1 entries");
+  TORCH_CHECK(B >= 1 && B <= M && M < (1L << 31) && dcv.size(1) == EP &&
+              a.numel() == EP && starts.numel() == M && attn.numel() == M &&
+              ds.numel() == M && da.numel() == B * EP,
+              "attention_packed_bwd shapes");
+  TORCH_CHECK((uintptr_t)ccv.data_ptr() % 16 == 0, "ccv must be 16-B aligned");
+  if (has_dattn) {
+    CHK_CUDA(dattn); CHK_CONTIG(dattn); CHK_DT(dattn, torch::kFloat32);
+    TORCH_CHECK(dattn.numel() == M, "dattn shape");
+  }
+  void* dccv_p = nullptr;
+  int* seg_p = nullptr;
+  if (dccv) {
+    CHK_CUDA(*dccv); CHK_CONTIG(*dccv); CHK_DT(*dccv, torch::kBFloat16);
+    TORCH_CHECK(dccv->numel() == M * EP, "dccv shape");
+    TORCH_CHECK((uintptr_t)dccv->data_ptr() % 16 == 0,
+                "dccv must be 16-B aligned");
+    dccv_p = dccv->data_ptr();
+  } else {
+    CHK_CUDA(*seg); CHK_CONTIG(*seg); CHK_DT(*seg, torch::kInt32);
+    TORCH_CHECK(seg->numel() == M, "seg shape");
+    seg_p = seg->data_ptr<int>();
+  }
+  launch_attention_packed_bwd(
+      dcv.data_ptr(), dcv_bf16 ? 1 : 0,
+      has_dattn ? dattn.data_ptr<float>() : nullptr, ccv.data_ptr(),
+      a.data_ptr<float>(), starts.data_ptr<int>(), offsets.data_ptr<int>(),
+      attn.data_ptr<float>(), dccv_p, ds.data_ptr<float>(), seg_p,
+      da.data_ptr<float>(), M, B, EP, (int)E, cur_stream());
+}
+
+void attention_packed_bwd_compact(
+    torch::Tensor dcv, torch::Tensor dattn, torch::Tensor ccv, torch::Tensor a,
+    torch::Tensor starts, torch::Tensor offsets, torch::Tensor attn,
+    torch::Tensor ds, torch::Tensor seg, torch::Tensor da, int64_t E,
+    bool has_dattn, int64_t chunk) {
+  attention_packed_bwd_impl(dcv, dattn, ccv, a, starts, offsets, attn,
+                            nullptr, ds, &seg, da, E, has_dattn, chunk);
+}
+
+void attention_packed_bwd(
+    torch::Tensor dcv, torch::Tensor dattn, torch::Tensor ccv, torch::Tensor a,
+    torch::Tensor starts, torch::Tensor offsets, torch::Tensor attn,
+    torch::Tensor dccv, torch::Tensor ds_ws, torch::Tensor da, int64_t E,
+    bool has_dattn, int64_t chunk) {
+  attention_packed_bwd_impl(dcv, dattn, ccv, a, starts, offsets, attn, &dccv,
+                            ds_ws, nullptr, da, E, has_dattn, chunk);
+}
+
+// combiner_bwd_recompute for a packed batch: the method of a row is
+// seg[row] (i32 [M], written by attention_packed_bwd_compact), dcv is
+// [B, 128] f32 or bf16.  Same grid and partial layout.
+void combiner_bwd_recompute_packed(
+    torch::Tensor attn, torch::Tensor ds, torch::Tensor dcv, torch::Tensor a,
+    torch::Tensor seg, torch::Tensor z, torch::Tensor out, torch::Tensor mean,
+    torch::Tensor rstd, torch::Tensor gamma, torch::Tensor beta,
+    torch::Tensor dz, torch::Tensor dgamma, torch::Tensor dbeta, int64_t E,
+    double p) {
+  CHK_CUDA(z); CHK_CONTIG(z); CHK_DT(z, torch::kBFloat16);
+  CHK_CUDA(out); CHK_CONTIG(out); CHK_DT(out, torch::kBFloat16);
+  CHK_CUDA(dz); CHK_CONTIG(dz); CHK_DT(dz, torch::kBFloat16);
+  CHK_CUDA(attn); CHK_CONTIG(attn); CHK_DT(attn, torch::kFloat32);
+  CHK_CUDA(ds); CHK_CONTIG(ds); CHK_DT(ds, torch::kFloat32);
+  CHK_CUDA(seg); CHK_CONTIG(seg); CHK_DT(seg, torch::kInt32);
+  CHK_CUDA(dcv); CHK_CONTIG(dcv);
+  CHK_CUDA(a); CHK_CONTIG(a); CHK_DT(a, torch::kFloat32);
+  CHK_CUDA(mean); CHK_CONTIG(mean); CHK_DT(mean, torch::kFloat32);
+  CHK_CUDA(rstd); CHK_CONTIG(rstd); CHK_DT(rstd, torch::kFloat32);
+  CHK_CUDA(gamma); CHK_CONTIG(gamma); CHK_DT(gamma, torch::kFloat32);
+  CHK_CUDA(beta); CHK_CONTIG(beta); CHK_DT(beta, torch::kFloat32);
+  CHK_CUDA(dgamma); CHK_CONTIG(dgamma); CHK_DT(dgamma, torch::kFloat32);
+  CHK_CUDA(dbeta); CHK_CONTIG(dbeta); CHK_DT(dbeta, torch::kFloat32);
+  const bool dcv_bf16 = dcv.scalar_type() == torch::kBFloat16;
+  TORCH_CHECK(dcv_bf16 || dcv.scalar_type() == torch::kFloat32,
+              "dcv must be f32 or bf16");
+  TORCH_CHECK(z.dim() == 2 && dcv.dim() == 2, "z must be [M, EP], dcv [B, EP]");
+  const long M = z.size(0);
+  const int EP = z.size(1);
+  const long B = dcv.size(0);
+  TORCH_CHECK(EP == 128 && B >= 1 && B <= M && M < (1L << 31) &&
+              E >= 1 && E <= EP && attn.numel() == M && ds.numel() == M &&
+              seg.numel() == M && dcv.size(1) == EP && a.numel() == EP &&
+              out.numel() == M * EP && dz.numel() == M * EP &&
+              mean.numel() == M && rstd.numel() == M && gamma.numel() == EP &&
+              beta.numel() == EP,
+              "combiner_bwd_recompute_packed shapes");
+  const long nblocks = std::min<long>((M + 3) / 4, 1024);
+  TORCH_CHECK(dgamma.numel() == nblocks * EP && dbeta.numel() == nblocks * EP,
+              "dgamma/dbeta partials must be [min(ceil(M/4), 1024), EP]");
+  launch_combiner_bwd_recompute_packed(
+      attn.data_ptr<float>(), ds.data_ptr<float>(), dcv.data_ptr(),
+      dcv_bf16 ? 1 : 0, a.data_ptr<float>(), seg.data_ptr<int>(), B,
+      z.data_ptr(), out.data_ptr(), mean.data_ptr<float>(),
+      rstd.data_ptr<float>(), gamma.data_ptr<float>(),
+      beta.data_ptr<float>(), dz.data_ptr(), dgamma.data_ptr<float>(),
+      dbeta.data_ptr<float>(), M, (int)E, (float)p, cur_stream());
 }
 
 void attention_bwd(torch::Tensor dcv, torch::Tensor dattn, torch::Tensor ccv,
@@ -1611,6 +1751,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attention_bwd_compact_reg", &attention_bwd_compact_reg);
   m.def("attention_pool_packed", &attention_pool_packed);
   m.def("combiner_bwd_recompute", &combiner_bwd_recompute);
+  m.def("attention_packed_bwd_compact", &attention_packed_bwd_compact);
+  m.def("attention_packed_bwd", &attention_packed_bwd);
+  m.def("combiner_bwd_recompute_packed", &combiner_bwd_recompute_packed);
   m.def("slab_sum2_f32", &slab_sum2_f32);
   m.def("loss_reduce", &loss_reduce);
   m.def("wgrad_reduce", &wgrad_reduce);

@@ -441,7 +441,12 @@ __device__ __forceinline__ float half_wave_reduce_sum(float x) {
 // L2-resident) and rebuilds bf16(attn*dcv + ds*a) in registers through
 // dccv_elem().  Grid, row-to-wave mapping and the dgamma/dbeta partial
 // layout are shared by all modes, so those sums keep their order.
-template <int MODE>
+// SEG (MODE 1/2 only) is the packed-batch form: methods are ragged, so the
+// method index comes from the row -> method map seg[row] that the packed
+// attention backward (K22) wrote, not from row / C; the C argument then
+// carries the method count B and only clamps the index.  Everything else
+// is the same code, so equal inputs give equal bits.
+template <int MODE, bool SEG = false>
 __global__ __launch_bounds__(256) void combiner_bwd_v2_kernel(
     const bf16* __restrict__ dout, const bf16* __restrict__ z,
     const bf16* __restrict__ out, const float* __restrict__ mean,
@@ -450,7 +455,8 @@ __global__ __launch_bounds__(256) void combiner_bwd_v2_kernel(
     float* __restrict__ dgamma_part, float* __restrict__ dbeta_part, long M,
     int E, float p, float inv1mp, const float* __restrict__ attn,
     const float* __restrict__ ds, const void* __restrict__ dcv,
-    const float* __restrict__ att_a, unsigned C) {
+    const float* __restrict__ att_a, unsigned C,
+    const int* __restrict__ seg = nullptr) {
   const int EP = 128;
   const int lane = threadIdx.x & (WAVE - 1);
   const int wave = threadIdx.x / WAVE;
@@ -481,7 +487,7 @@ __global__ __launch_bounds__(256) void combiner_bwd_v2_kernel(
   // divide per thread, then a step of 2*pstride rows per iteration);
   // M < 2^31 is checked by the caller
   unsigned mb = 0, mrem = 0, mb_step = 0, mrem_step = 0;
-  if (MODE != 0) {
+  if (MODE != 0 && !SEG) {
     const unsigned row0 = (unsigned)(2 * pr + half);
     mb = row0 / C;
     mrem = row0 - mb * C;
@@ -501,7 +507,7 @@ __global__ __launch_bounds__(256) void combiner_bwd_v2_kernel(
       if (MODE == 0) {
         dy4 = *(const bf16x4*)(dout + row * EP + c0);
       } else {
-        const unsigned b = mb;
+        const unsigned b = SEG ? min((unsigned)seg[row], C - 1u) : mb;
         const float at = attn[row];
         const float dsc = ds[row];
         f32x4 dc;
@@ -548,7 +554,7 @@ __global__ __launch_bounds__(256) void combiner_bwd_v2_kernel(
       }
       *(bf16x4*)(dz + row * EP + c0) = o;
     }
-    if (MODE != 0) {
+    if (MODE != 0 && !SEG) {
       mb += mb_step;
       mrem += mrem_step;
       if (mrem >= C) {
@@ -791,6 +797,30 @@ void launch_combiner_bwd_recompute(const float* attn, const float* ds,
         nullptr, (const bf16*)z, (const bf16*)out, mean, rstd, gamma, beta,
         (bf16*)dz, dgamma, dbeta, M, E, p, inv1mp, attn, ds, dcv, att_a,
         (unsigned)C);
+}
+
+// The same for a packed batch: seg[M] maps a row to its method (written by
+// the compact K22), dcv has B rows.  Same grid, same partial layout.
+void launch_combiner_bwd_recompute_packed(
+    const float* attn, const float* ds, const void* dcv, int dcv_bf16,
+    const float* att_a, const int* seg, long B, const void* z,
+    const void* out, const float* mean, const float* rstd,
+    const float* gamma, const float* beta, void* dz, float* dgamma,
+    float* dbeta, long M, int E, float p, hipStream_t stream) {
+  const int block = 256;
+  const int wpb = block / WAVE;
+  const int grid = (int)min((M + wpb - 1) / wpb, (long)COMBINER_BWD_MAX_GRID);
+  const float inv1mp = p > 0.f ? 1.0f / (1.0f - p) : 1.0f;
+  if (dcv_bf16)
+    combiner_bwd_v2_kernel<2, true><<<grid, block, 0, stream>>>(
+        nullptr, (const bf16*)z, (const bf16*)out, mean, rstd, gamma, beta,
+        (bf16*)dz, dgamma, dbeta, M, E, p, inv1mp, attn, ds, dcv, att_a,
+        (unsigned)B, seg);
+  else
+    combiner_bwd_v2_kernel<1, true><<<grid, block, 0, stream>>>(
+        nullptr, (const bf16*)z, (const bf16*)out, mean, rstd, gamma, beta,
+        (bf16*)dz, dgamma, dbeta, M, E, p, inv1mp, attn, ds, dcv, att_a,
+        (unsigned)B, seg);
 }
 
 }  // extern "C"

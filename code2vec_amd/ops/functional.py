@@ -162,14 +162,17 @@ class GatherConcat(torch.autograd.Function):
     """
 
     @classmethod
-    def apply(cls, starts, paths, ends, term_w, path_w, training=True):
+    def apply(cls, starts, paths, ends, term_w, path_w, training=True,
+              row_capacity=None):
         # forward() itself always runs with grad mode off: whether a
         # backward can follow is only visible out here
         track = bool(training) and torch.is_grad_enabled()
-        return super().apply(starts, paths, ends, term_w, path_w, track)
+        return super().apply(starts, paths, ends, term_w, path_w, track,
+                             row_capacity)
 
     @staticmethod
-    def forward(ctx, starts, paths, ends, term_w, path_w, track=False):
+    def forward(ctx, starts, paths, ends, term_w, path_w, track=False,
+                row_capacity=None):
         B, C = starts.shape
         TS = term_w.shape[1]
         PS = path_w.shape[1]
@@ -180,7 +183,8 @@ class GatherConcat(torch.autograd.Function):
         # the grouping goes first so that, on its side stream, it runs
         # under the gather and everything after it
         ctx.group_ticket = (
-            _launch_table_grouping(starts, paths, ends, term_w, path_w)
+            _launch_table_grouping(starts, paths, ends, term_w, path_w,
+                                   row_capacity)
             if track else None)
         ext().gather_concat_fwd(starts, paths, ends, term_w, path_w, out)
         ctx.save_for_backward(starts, paths, ends)
@@ -197,7 +201,7 @@ class GatherConcat(torch.autograd.Function):
             path_shape, ctx.param_keys[0], ctx.param_keys[1],
             ticket=ctx.group_ticket
         )
-        return None, None, None, dterm, dpath, None
+        return None, None, None, dterm, dpath, None, None
 
 
 def _scatter_embedding_grads(starts, paths, ends, gout, term_shape,
@@ -425,12 +429,22 @@ def _grouping_applies(term_key, path_key) -> bool:
                for k in (term_key, path_key))
 
 
-def _launch_table_grouping(starts, paths, ends, term_w, path_w):
+def _launch_table_grouping(starts, paths, ends, term_w, path_w,
+                           row_capacity=None):
     """Group both tables' indices for the backward of this forward and
     return the ticket that backward adopts them with, or None where the
     deferred table gradient does not apply (then backward groups per table
     as before).  At most one grouping is outstanding: one that no backward
-    adopted is retired first."""
+    adopted is retired first.
+
+    ``row_capacity`` (packed batches, whose row count M differs from step
+    to step): the row-sized buffers are allocated once for that many rows
+    and the kernels get [:n] views, so the scratch cache does not grow by a
+    set of buffers per distinct M.  None keeps the padded path's keys."""
+    if row_capacity is not None and starts.numel() > row_capacity:
+        raise ValueError(
+            f"packed batch has {starts.numel()} rows, over the row capacity "
+            f"{row_capacity} its scratch was sized for")
     if not (_GROUP_TABLES and starts.is_cuda and term_w.requires_grad
             and path_w.requires_grad
             and _grouping_applies(term_w.data_ptr(), path_w.data_ptr())
@@ -452,8 +466,14 @@ def _launch_table_grouping(starts, paths, ends, term_w, path_w):
         if stale is not None:
             discard_deferred(stale)
         cursor = _scratch_i32(f"cursor_{tag}", rows, dev, zero=False)
-        sorted_idx = _scratch_i32(f"gsorted_{tag}", n, dev, zero=False)
-        perm = _scratch_i64(f"gperm_{tag}", n, dev)
+        if row_capacity is None:
+            sorted_idx = _scratch_i32(f"gsorted_{tag}", n, dev, zero=False)
+            perm = _scratch_i64(f"gperm_{tag}", n, dev)
+        else:
+            cap = (n // M) * int(row_capacity)
+            sorted_idx = _scratch_i32(f"gsorted_cap_{tag}", cap, dev,
+                                      zero=False)[:n]
+            perm = _scratch_i64(f"gperm_cap_{tag}", cap, dev)[:n]
         g.tables[tag] = (sorted_idx, perm, counts, cursor)
         bufs[tag] = rows
     spart = _scratch_i32(
@@ -918,6 +938,190 @@ def attention_pool_packed(ccv: torch.Tensor, a: torch.Tensor,
     ext().attention_pool_packed(ccv, a, starts.reshape(-1), offsets, cv, cvb,
                                 attn, int(E), ATTN_PACKED_CHUNK)
     return cv, cvb, attn
+
+
+def packed_offsets(lengths, M: int, device, offsets=None):
+    """Host check of a packed batch's lengths (every n >= 1, sum == M;
+    ValueError before anything is launched) and the device offsets [B+1]
+    i32 the segmented kernels trust.  ``offsets`` may hand in device
+    offsets a loader already built from these same lengths (then no
+    host-to-device copy happens here); only their place and size are
+    checked.  Returns (lens CPU i64, offsets)."""
+    from . import reference as R
+
+    lens = R.check_packed_lengths(lengths, M)
+    B = lens.numel()
+    if offsets is None:
+        offsets = torch.zeros(B + 1, dtype=torch.int32)
+        offsets[1:] = torch.cumsum(lens, 0)
+        offsets = offsets.to(device)
+    elif (offsets.device != torch.device(device)
+          or offsets.dtype != torch.int32 or offsets.numel() != B + 1
+          or not offsets.is_contiguous()):
+        raise ValueError(
+            f"packed offsets must be a contiguous int32 tensor of "
+            f"{B + 1} entries on {device}")
+    return lens, offsets
+
+
+class AttentionPoolPacked(torch.autograd.Function):
+    """K21 forward + dense K22 backward: the attention pool over a packed
+    batch as an autograd node, for any EP (a multiple of 32, <= 384).
+
+    ccv: bf16 [M, EP]; a: f32 [EP]; starts: i32 [M]; offsets: i32 [B+1] on
+    the device (packed_offsets).  Returns cv f32 [B, EP] and attn f32 [M].
+    """
+
+    @staticmethod
+    def forward(ctx, ccv, a, starts, offsets, E: int):
+        M, EP = ccv.shape
+        B = offsets.numel() - 1
+        dev = ccv.device
+        cv = torch.empty(B, EP, dtype=torch.float32, device=dev)
+        cvb = torch.empty(B, EP, dtype=torch.bfloat16, device=dev)
+        attn = torch.empty(M, dtype=torch.float32, device=dev)
+        ext().attention_pool_packed(ccv, a, starts, offsets, cv, cvb, attn,
+                                    int(E), ATTN_PACKED_CHUNK)
+        ctx.save_for_backward(ccv, a, starts, offsets, attn)
+        ctx.E = int(E)
+        ctx.set_materialize_grads(False)
+        return cv, attn
+
+    @staticmethod
+    def backward(ctx, dcv, dattn):
+        ccv, a, starts, offsets, attn = ctx.saved_tensors
+        M, EP = ccv.shape
+        B = offsets.numel() - 1
+        dev = ccv.device
+        if dcv is None:
+            dcv = torch.zeros(B, EP, dtype=torch.float32, device=dev)
+        dccv = torch.empty_like(ccv)
+        # where a method longer than the LDS chunk parks its g/ds
+        ds_ws = torch.empty(M, dtype=torch.float32, device=dev)
+        da_p = torch.empty(B, EP, dtype=torch.float32, device=dev)
+        has_dattn = dattn is not None
+        ext().attention_packed_bwd(
+            dcv.contiguous(), dattn.contiguous() if has_dattn else _NONE_T,
+            ccv, a, starts, offsets, attn, dccv, ds_ws, da_p, ctx.E,
+            has_dattn, ATTN_PACKED_CHUNK)
+        return dccv, _slab_sum(da_p), None, None, None
+
+
+class CombinerAttentionPoolPacked(torch.autograd.Function):
+    """CombinerAttentionPool over a packed batch (EP = 128): combiner_fwd
+    on the M rows (dropout in training), then K21; returns (cv f32 [B, EP],
+    attn [M], cvb bf16 [B, EP]).  Backward is the compact K22 (ds [M], the
+    row -> method map seg [M] and the da partials), then
+    combiner_bwd_recompute_packed, which rebuilds each dccv element in
+    registers through dccv_elem with the method taken from seg, then the
+    shared dx/dw.  dccv [M, EP] is never written."""
+
+    @staticmethod
+    def forward(ctx, x, w, gamma, beta, a, starts, offsets, E: int, p: float,
+                training: bool):
+        M = x.shape[0]
+        EP = w.shape[0]
+        B = offsets.numel() - 1
+        assert EP == 128 and starts.numel() == M
+        dev = x.device
+        out = torch.empty(M, EP, dtype=torch.bfloat16, device=dev)
+        z = torch.empty(M, EP, dtype=torch.bfloat16, device=dev)
+        mean = torch.empty(M, dtype=torch.float32, device=dev)
+        rstd = torch.empty(M, dtype=torch.float32, device=dev)
+        p_eff = float(p) if training else 0.0
+        seed, off_t = (_philox_state(dev) if p_eff > 0.0
+                       else (0, _philox_state(dev)[1]))
+        ext().combiner_fwd(x, w, gamma, beta, out, z, mean, rstd, E, p_eff,
+                           seed, off_t, _FWD_EPI)
+        cv = torch.empty(B, EP, dtype=torch.float32, device=dev)
+        cvb = torch.empty(B, EP, dtype=torch.bfloat16, device=dev)
+        attn = torch.empty(M, dtype=torch.float32, device=dev)
+        ext().attention_pool_packed(out, a, starts, offsets, cv, cvb, attn,
+                                    int(E), ATTN_PACKED_CHUNK)
+        ctx.save_for_backward(x, w, gamma, beta, a, starts, offsets, z, mean,
+                              rstd, out, attn)
+        ctx.meta = (int(E), p_eff)
+        ctx.set_materialize_grads(False)
+        return cv, attn, cvb
+
+    @staticmethod
+    def backward(ctx, dcv32, dattn, dcvb):
+        (x, w, gamma, beta, a, starts, offsets, z, mean, rstd, out,
+         attn) = ctx.saved_tensors
+        E, p = ctx.meta
+        M, EP = z.shape
+        B = offsets.numel() - 1
+        dev = z.device
+        if dcv32 is not None and dcvb is not None:
+            dcv = dcv32 + dcvb  # f32 sum, as autograd's accumulation did
+        elif dcvb is not None:
+            dcv = dcvb          # bf16, read by the kernels as is
+        elif dcv32 is not None:
+            dcv = dcv32
+        else:
+            dcv = torch.zeros(B, EP, dtype=torch.float32, device=dev)
+        dcv = dcv.contiguous()
+        ds = torch.empty(M, dtype=torch.float32, device=dev)
+        seg = torch.empty(M, dtype=torch.int32, device=dev)
+        da_p = torch.empty(B, EP, dtype=torch.float32, device=dev)
+        has_dattn = dattn is not None
+        ext().attention_packed_bwd_compact(
+            dcv, dattn.contiguous() if has_dattn else _NONE_T, out, a,
+            starts, offsets, attn, ds, seg, da_p, E, has_dattn,
+            ATTN_PACKED_CHUNK)
+        da = _slab_sum(da_p)
+        dz = torch.empty(M, EP, dtype=torch.bfloat16, device=dev)
+        nblocks = min((M + 4 - 1) // 4, 1024)
+        dgamma_p = torch.empty(nblocks, EP, dtype=torch.float32, device=dev)
+        dbeta_p = torch.empty(nblocks, EP, dtype=torch.float32, device=dev)
+        ext().combiner_bwd_recompute_packed(attn, ds, dcv, a, seg, z, out,
+                                            mean, rstd, gamma, beta, dz,
+                                            dgamma_p, dbeta_p, E, p)
+        dgamma, dbeta = _slab_sum_pair(dgamma_p, dbeta_p)
+        dx, dw = _combiner_dx_dw(x, w, dz)
+        return dx, dw, dgamma, dbeta, da, None, None, None, None, None
+
+
+def _check_packed_pool_args(name, rows, EP, starts):
+    if EP % 32 != 0 or not 32 <= EP <= 384:
+        raise ValueError(
+            f"{name}: EP must be a multiple of 32 in 32..384, got {EP}")
+    if starts.numel() != rows:
+        raise ValueError(
+            f"{name}: starts has {starts.numel()} entries for {rows} rows")
+
+
+def attention_pool_packed_train(ccv, a, starts, lengths, E: int,
+                                offsets=None):
+    """Differentiable attention_pool_packed (AttentionPoolPacked): the
+    lengths are checked on the host first, as there.  Returns (cv f32
+    [B, EP], attn f32 [M])."""
+    if ccv.dim() != 2:
+        raise ValueError(
+            f"attention_pool_packed_train: ccv must be [M, EP], got "
+            f"{tuple(ccv.shape)}")
+    M, EP = ccv.shape
+    _, offsets = packed_offsets(lengths, M, ccv.device, offsets)
+    _check_packed_pool_args("attention_pool_packed_train", M, EP, starts)
+    return AttentionPoolPacked.apply(ccv, a, starts.reshape(-1).contiguous(),
+                                     offsets, int(E))
+
+
+def combiner_attention_pool_packed(x, w, gamma, beta, a, starts, lengths,
+                                   E: int, p: float, training: bool,
+                                   offsets=None):
+    """CombinerAttentionPoolPacked behind the host check of the lengths
+    (EP = 128).  Returns (cv f32 [B, EP], attn f32 [M], cvb bf16)."""
+    M = x.shape[0]
+    _, offsets = packed_offsets(lengths, M, x.device, offsets)
+    if w.shape[0] != 128:
+        raise ValueError(
+            f"combiner_attention_pool_packed: EP must be 128, got "
+            f"{w.shape[0]}")
+    _check_packed_pool_args("combiner_attention_pool_packed", M, 128, starts)
+    return CombinerAttentionPoolPacked.apply(
+        x, w, gamma, beta, a, starts.reshape(-1).contiguous(), offsets,
+        int(E), float(p), bool(training))
 
 
 class CombinerAttentionPool(torch.autograd.Function):

@@ -80,6 +80,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "export (useful for pure throughput/F1 benchmark "
                         "runs on top11-scale corpora where the text export "
                         "dominates wall time)")
+    p.add_argument("--pack_batches", action="store_true", default=False,
+                   help="train on packed batches: each method's trailing "
+                        "PAD contexts are stripped and no pad row is "
+                        "processed (single process only; evaluation and "
+                        "export stay padded; path_contexts_per_sec then "
+                        "counts real rows)")
     p.add_argument("--init_model", type=str, default=None,
                    help="warm-start from a code2vec.model checkpoint "
                         "(reference state_dict format)")
