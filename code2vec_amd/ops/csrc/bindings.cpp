@@ -34,9 +34,10 @@ void launch_adam_table_bf16(void*, const void*, const long*, int*, const int*,
                             float, float, float, float, float, int,
                             hipStream_t);
 long group_tables_partials(long, long);
+long group_tables_tmp(long, long, long);
 void launch_group_tables(const int*, const int*, const int*, long, int, int,
                          int*, int*, int*, int*, int*, int*, long*, int*,
-                         long*, hipStream_t);
+                         long*, int*, hipStream_t);
 void launch_embed_scatter_heavy_pair(const int*, const long*, const int*,
                                      float*, int, const int*, const long*,
                                      const int*, float*, int, const void*,
@@ -1556,6 +1557,7 @@ struct GroupStream {
   hipStream_t side = nullptr;
   hipEvent_t ready = nullptr;  // current stream -> side stream
   hipEvent_t done = nullptr;   // side stream -> adopting/retiring stream
+  torch::Tensor tmp;           // scratch a side-stream chain allocated itself
 };
 std::map<int, GroupStream>& group_streams() {
   static std::map<int, GroupStream> m;
@@ -1585,14 +1587,17 @@ void check_i32(const torch::Tensor& t, long n, const char* what) {
 // Returns true if the chain went to the side stream: the consumer must then
 // call group_tables_wait() on its stream before touching any output.  While
 // the current stream is capturing, or with side_stream false, the chain is
-// launched on the current stream.
+// launched on the current stream.  ``tmp`` is the two-level sort's scratch
+// (group_tables_tmp_len ints); a caller on the hot path passes a persistent
+// buffer, without it one is allocated here.
 bool group_tables(torch::Tensor starts, torch::Tensor paths,
                   torch::Tensor ends, torch::Tensor counts_t,
                   torch::Tensor counts_p, torch::Tensor cursor_t,
                   torch::Tensor cursor_p, torch::Tensor partial,
                   torch::Tensor sorted_t, torch::Tensor perm_t,
                   torch::Tensor sorted_p, torch::Tensor perm_p,
-                  int64_t rows_t, int64_t rows_p, bool side_stream) {
+                  int64_t rows_t, int64_t rows_p, bool side_stream,
+                  c10::optional<torch::Tensor> tmp) {
   const long M = starts.numel();
   TORCH_CHECK(M > 0 && 2 * M < (1L << 31), "group_tables: bad entry count");
   TORCH_CHECK(rows_t > 0 && rows_p > 0 && rows_t < (1L << 31) &&
@@ -1628,13 +1633,32 @@ bool group_tables(torch::Tensor starts, torch::Tensor paths,
       on_side = true;
     }
   }
+  const long tmp_len = group_tables_tmp(M, rows_t, rows_p);
+  torch::Tensor scratch;
+  if (tmp.has_value()) {
+    scratch = *tmp;
+    check_i32(scratch, tmp_len, "tmp");
+    TORCH_CHECK((uintptr_t)scratch.data_ptr() % 8 == 0,
+                "group_tables: tmp must be 8-byte aligned");
+  } else {
+    scratch = torch::empty({tmp_len}, starts.options());
+    if (on_side) {
+      // the allocator knows the block on the current stream only: keep it
+      // until the next chain, and free the previous one no earlier than
+      // the current stream is ordered after the chain that used it
+      if (gs->tmp.defined())
+        C10_HIP_CHECK(hipStreamWaitEvent(cur.stream(), gs->done, 0));
+      gs->tmp = scratch;
+    }
+  }
   launch_group_tables(
       starts.data_ptr<int>(), paths.data_ptr<int>(), ends.data_ptr<int>(), M,
       (int)rows_t, (int)rows_p, counts_t.data_ptr<int>(),
       counts_p.data_ptr<int>(), cursor_t.data_ptr<int>(),
       cursor_p.data_ptr<int>(), partial.data_ptr<int>(),
       sorted_t.data_ptr<int>(), perm_t.data_ptr<long>(),
-      sorted_p.data_ptr<int>(), perm_p.data_ptr<long>(), launch_on);
+      sorted_p.data_ptr<int>(), perm_p.data_ptr<long>(),
+      scratch.data_ptr<int>(), launch_on);
   if (on_side) C10_HIP_CHECK(hipEventRecord(gs->done, gs->side));
   return on_side;
 }
@@ -1650,6 +1674,10 @@ void group_tables_wait() {
 
 int64_t group_tables_partials_len(int64_t rows_t, int64_t rows_p) {
   return group_tables_partials(rows_t, rows_p);
+}
+
+int64_t group_tables_tmp_len(int64_t M, int64_t rows_t, int64_t rows_p) {
+  return group_tables_tmp(M, rows_t, rows_p);
 }
 
 // embed_scatter_heavy for both tables of one group_tables record pair:
@@ -1799,7 +1827,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adam_table_bf16", &adam_table_bf16);
   m.def("adam_step_f32_multi", &adam_step_f32_multi);
   m.def("adam_table_bf16_keep_counts", &adam_table_bf16_keep_counts);
-  m.def("group_tables", &group_tables);
+  m.def("group_tables", &group_tables, py::arg("starts"), py::arg("paths"),
+        py::arg("ends"), py::arg("counts_t"), py::arg("counts_p"),
+        py::arg("cursor_t"), py::arg("cursor_p"), py::arg("partial"),
+        py::arg("sorted_t"), py::arg("perm_t"), py::arg("sorted_p"),
+        py::arg("perm_p"), py::arg("rows_t"), py::arg("rows_p"),
+        py::arg("side_stream"), py::arg("tmp") = py::none());
+  m.def("group_tables_tmp_len", &group_tables_tmp_len);
   m.def("group_tables_wait", &group_tables_wait);
   m.def("group_tables_partials_len", &group_tables_partials_len);
   m.def("embed_scatter_heavy_pair", &embed_scatter_heavy_pair);

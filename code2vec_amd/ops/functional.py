@@ -121,6 +121,9 @@ _TABLE_ADAM_HEAVY = int(os.environ.get("C2V_TABLE_ADAM_HEAVY", "64"))
 # groups both index lists at FORWARD time — they depend on the batch only —
 # and the backward adopts the result (see _launch_table_grouping).
 # C2V_GROUP_TABLES=0 keeps the per-table chain inside backward.
+# C2V_GROUP_SORT=0 keeps the merged chain's global-atomic kernels instead of
+# the two-level sort by LDS buckets (read in index_group.hip, as are the
+# sweep switches C2V_GROUP_R and C2V_GROUP_TILE).
 # C2V_GROUP_STREAM=1 launches the merged chain on a side stream so that it
 # overlaps the step; measured SLOWER than launching it on the forward's own
 # stream (1.160-1.176 against 1.128-1.136 ms/step at top11, parent
@@ -480,10 +483,20 @@ def _launch_table_grouping(starts, paths, ends, term_w, path_w,
         "gscanp", int(ext().group_tables_partials_len(bufs["term"],
                                                       bufs["path"])),
         dev, zero=False)
+    # the two-level sort's M-sized scratch: persistent like the records,
+    # one buffer per row capacity on the packed path
+    tmp_n = int(ext().group_tables_tmp_len(M, bufs["term"], bufs["path"]))
+    if row_capacity is None:
+        gtmp = _scratch_i32("gtmp", tmp_n, dev, zero=False)
+    else:
+        gtmp = _scratch_i32(
+            "gtmp_cap", int(ext().group_tables_tmp_len(
+                int(row_capacity), bufs["term"], bufs["path"])),
+            dev, zero=False)[:tmp_n]
     st, sp = g.tables["term"], g.tables["path"]
     g.on_side = bool(ext().group_tables(
         starts, paths, ends, st[2], sp[2], st[3], sp[3], spart, st[0], st[1],
-        sp[0], sp[1], bufs["term"], bufs["path"], _GROUP_STREAM))
+        sp[0], sp[1], bufs["term"], bufs["path"], _GROUP_STREAM, gtmp))
     # the side-stream kernels read these: they stay alive here until a
     # backward adopts the grouping (whose ctx holds them too) or it is
     # retired, both of which order the current stream after the kernels

@@ -8,7 +8,7 @@ env vars read by ops/functional.py.  Usage (on a GPU box):
 (scatter + cast_clear + adam_bf16 vs the row-gathering table Adam) and
 ``bwd_fusions`` (one-launch reductions, compact attention backward and
 recomputing combiner backward vs what they replace) and ``group_tables``
-(both tables' counting sort: per-table chains vs the one merged chain) and
+(both tables' counting sort: the global-atomic chain vs the LDS buckets) and
 ``attn_stream`` (streaming attention forward/backward and the combiner's
 score-emitting flush vs the tiled kernels) and ``head_bwd_pipe`` (the
 pipelined head backward and wgrad kernels vs the ones they replace) are
@@ -151,18 +151,24 @@ def bench_table_adam(dev, results, rounds=5):
 
 
 def bench_group_tables(dev, results, rounds=5):
-    """Counting sort of both tables' index lists, old against new on the
-    SAME persistent buffers, alternating within each round (median / min):
-      old: torch.cat + per table count, scan, scatter_group (13 launches
-           with the two histogram clears the table Adam pays afterwards)
-      new: group_tables on the current stream + clear_i32_pair (5 launches)
-    at the top11 shapes with uniform indices over [1, rows) and with a
-    ragged batch (half <PAD/>).  Both variants leave the histograms zero."""
+    """Counting sort of both tables' index lists: the global-atomic chain
+    (C2V_GROUP_SORT=0: count, scan partials, scan apply, group) against the
+    two-level sort by LDS buckets, on the SAME persistent buffers,
+    alternating within each round (median / min).  Both are followed by the
+    clear_i32_pair the table Adam pays afterwards, so both leave the
+    histograms zero.  Top11 shapes; inputs: uniform indices over [1, rows),
+    a ragged batch (half <PAD/>), and a hot row (25 % of all entries on one
+    index >= 2).  C2V_KBENCH_GROUP_SWEEP=1 adds the R x tile sweep of the
+    new chain (the launcher reads the switches on every call)."""
     from code2vec_amd.ops import ext
 
     M, T, P = 1024 * 200, 360632, 342846
     g = torch.Generator(device=dev).manual_seed(0)
-    for tag in ("uniform", "half-pad"):
+    switches = ("C2V_GROUP_SORT", "C2V_GROUP_R", "C2V_GROUP_TILE")
+    saved = {k: os.environ.pop(k, None) for k in switches}
+    sweep = [(r, t) for r in (1024, 2048, 4096) for t in (1024, 2048, 4096)] \
+        if os.environ.get("C2V_KBENCH_GROUP_SWEEP") == "1" else []
+    for tag in ("uniform", "half-pad", "hot-row"):
         starts = torch.randint(1, T, (1024, 200), generator=g, device=dev,
                                dtype=torch.int32)
         paths = torch.randint(1, P, (1024, 200), generator=g, device=dev,
@@ -172,6 +178,10 @@ def bench_group_tables(dev, results, rounds=5):
         if tag == "half-pad":
             for t in (starts, paths, ends):
                 t[:, 100:] = 0
+        if tag == "hot-row":
+            for t in (starts, paths, ends):
+                hot = torch.rand(t.shape, generator=g, device=dev) < 0.25
+                t[hot] = 12345
         bufs = {}
         for name, rows, n in (("term", T + 1, 2 * M), ("path", P + 1, M)):
             bufs[name] = (
@@ -182,31 +192,39 @@ def bench_group_tables(dev, results, rounds=5):
         spart = Fn._scratch_i32(
             "gscanp", int(ext().group_tables_partials_len(T + 1, P + 1)),
             dev, zero=False)
+        gtmp = Fn._scratch_i32(
+            "gtmp", int(ext().group_tables_tmp_len(M, T + 1, P + 1)), dev,
+            zero=False)
         bt, bp = bufs["term"], bufs["path"]
 
-        def old():
-            idx_se = torch.cat([starts.view(-1), ends.view(-1)])
-            a = Fn._group_by_index(idx_se, T, pool_tag="term",
-                                   with_cursor=True)
-            b = Fn._group_by_index(paths.view(-1), P, pool_tag="path",
-                                   with_cursor=True)
-            a[2].zero_()
-            b[2].zero_()
-
-        def new():
+        def chain():
             ext().group_tables(starts, paths, ends, bt[2], bp[2], bt[3],
                                bp[3], spart, bt[0], bt[1], bp[0], bp[1],
-                               T + 1, P + 1, False)
+                               T + 1, P + 1, False, gtmp)
             ext().clear_i32_pair(bt[2], bp[2])
 
-        t = {"old": [], "new": []}
+        def run(env):
+            for k in switches:
+                os.environ.pop(k, None)
+            os.environ.update(env)
+            return timeit(chain, iters=50)
+
+        variants = {"old": {"C2V_GROUP_SORT": "0"}, "new": {}}
+        for r, tl in sweep:
+            variants[f"new R={r} tile={tl}"] = {"C2V_GROUP_R": str(r),
+                                                "C2V_GROUP_TILE": str(tl)}
+        t = {name: [] for name in variants}
         for _ in range(rounds):
-            t["old"].append(timeit(old, iters=50))
-            t["new"].append(timeit(new, iters=50))
+            for name, env in variants.items():
+                t[name].append(run(env))
         for name, vals in t.items():
             vals.sort()
             results[f"group_tables({tag}) {name} med"] = vals[rounds // 2]
             results[f"group_tables({tag}) {name} min"] = vals[0]
+    for k in switches:
+        os.environ.pop(k, None)
+        if saved[k] is not None:
+            os.environ[k] = saved[k]
 
 
 def bench_bwd_fusions(dev, results, rounds=5):
