@@ -10,7 +10,7 @@ launch-bound export loop.
 
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import Optional
 
 import torch
 
@@ -20,11 +20,21 @@ class GraphedInference:
 
     Tail batches smaller than B are padded with pad rows (starts=0 =>
     uniform attention over an all-pad bag) and sliced after replay.
+
+    With ``topk`` set the capture is ``model.encode`` + ``model.head_topk``
+    (K23) instead of ``forward``: no [B, L] logits exist, the label is
+    unused, and ``run`` returns ((vals, idx, lse), code_vector, attention).
+    What ``head_topk`` reads besides the parameters (the angular head's
+    unit-row image) lives in one buffer that the model refreshes in place;
+    ``run`` asks for that refresh before every replay, so the graph never
+    holds a dead address and follows a weight change as the default head's
+    graph does.
     """
 
     def __init__(self, model, batch_size: int, device,
-                 warmup_iters: int = 3) -> None:
+                 warmup_iters: int = 3, topk: Optional[int] = None) -> None:
         self.model = model
+        self.topk = topk
         self.B = batch_size
         self.C = model.option.max_path_length
         self.device = device
@@ -40,17 +50,25 @@ class GraphedInference:
         s.wait_stream(torch.cuda.current_stream(device))
         with torch.cuda.stream(s), torch.no_grad():
             for _ in range(warmup_iters):
-                self.model(self.starts, self.paths, self.ends, self.label)
+                self._forward()
         torch.cuda.current_stream(device).wait_stream(s)
 
         self.graph = torch.cuda.CUDAGraph()
         with torch.no_grad():
             with torch.cuda.graph(self.graph):
-                out = self.model(self.starts, self.paths, self.ends, self.label)
+                out = self._forward()
         self.outputs, self.code_vector, self.attention = out
 
+    def _forward(self):
+        if self.topk is None:
+            return self.model(self.starts, self.paths, self.ends, self.label)
+        cv, cvb, attn = self.model.encode(self.starts, self.paths, self.ends)
+        return self.model.head_topk(cvb, self.topk), cv, attn
+
     @torch.no_grad()
-    def run(self, starts, paths, ends, label) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    def run(self, starts, paths, ends, label=None):
+        """(outputs [n, L], code_vector, attention) of the first n rows; with
+        ``topk`` set, outputs is (vals, idx, lse) and ``label`` is unused."""
         n = starts.shape[0]
         assert n <= self.B
         for dst, src, fill in (
@@ -61,10 +79,19 @@ class GraphedInference:
             dst[:n].copy_(src.to(torch.int32), non_blocking=True)
             if n < self.B:
                 dst[n:].fill_(fill)
-        self.label[:n].copy_(label, non_blocking=True)
-        if n < self.B:
-            self.label[n:].zero_()
+        if self.topk is not None:
+            self.model.prepare_head_topk()
+        else:
+            self.label[:n].copy_(label, non_blocking=True)
+            if n < self.B:
+                self.label[n:].zero_()
         self.graph.replay()
+        if self.topk is not None:
+            return (
+                tuple(t[:n] for t in self.outputs),
+                self.code_vector[:n],
+                self.attention[:n],
+            )
         return (
             self.outputs[:n],
             self.code_vector[:n],
@@ -72,11 +99,12 @@ class GraphedInference:
         )
 
 
-def graphed_export_forward(model, batch_size: int, device) -> Optional[GraphedInference]:
+def graphed_export_forward(model, batch_size: int, device,
+                           topk: Optional[int] = None) -> Optional[GraphedInference]:
     """Build a GraphedInference if on GPU with the HIP backend; else None."""
     if device.type != "cuda" or getattr(model, "backend", "") != "hip":
         return None
     try:
-        return GraphedInference(model, batch_size, device)
+        return GraphedInference(model, batch_size, device, topk=topk)
     except Exception:  # capture unsupported -> eager fallback
         return None

@@ -18,6 +18,11 @@ path-contexts: batches are packed (``DatasetBuilder.build_packed``,
 eagerly, because their shapes vary.  Nothing is padded, subsampled or
 drawn from an RNG, and a method's code vector and attention do not depend
 on which other methods share its batch.
+
+With ``fused_head=True`` names come from ``model.encode`` +
+``model.head_topk`` (K23): the [B, L] logits are never allocated, on the
+padded, the graphed and the packed path alike, and the angular-margin head
+is accepted, scored by its margin-free logits inverse_temp * cosine.
 """
 
 from __future__ import annotations
@@ -57,9 +62,10 @@ class Predictor:
                  top_contexts: int = 5, batch_size: int = 32,
                  use_graph: bool = True, seed: int = 123,
                  all_contexts: bool = False,
-                 max_batch_contexts: Optional[int] = None) -> None:
+                 max_batch_contexts: Optional[int] = None,
+                 fused_head: bool = False) -> None:
         option = model.option
-        if option.angular_margin_loss:
+        if option.angular_margin_loss and not fused_head:
             raise ValueError(ANGULAR_PREDICT_ERROR)
         for name, v in (("topk", topk), ("top_contexts", top_contexts)):
             if not 1 <= v <= R.ROW_TOPK_MAX_K:
@@ -84,9 +90,11 @@ class Predictor:
         self.seed = seed
         self.all_contexts = all_contexts
         self.max_batch_contexts = max_batch_contexts
+        self.fused_head = fused_head
         model.eval()
         self.graphed = (
-            graphed_export_forward(model, batch_size, self.device)
+            graphed_export_forward(model, batch_size, self.device,
+                                   topk=topk if fused_head else None)
             if use_graph and not all_contexts else None
         )
         self._builders = {}
@@ -94,16 +102,25 @@ class Predictor:
     # ------------------------------------------------------------------
     @torch.no_grad()
     def _forward(self, starts, paths, ends):
+        """(outputs, code_vector, attention); with ``fused_head`` outputs
+        is head_topk's (vals, idx, lse) instead of the logits."""
         label = torch.zeros(starts.shape[0], dtype=torch.int64,
                             device=self.device)
         if (self.graphed is not None and starts.shape[0] <= self.graphed.B
                 and starts.shape[1] == self.graphed.C):
             return self.graphed.run(starts, paths, ends, label)
+        if self.fused_head:
+            cv, cvb, attn = self.model.encode(starts, paths, ends)
+            return self.model.head_topk(cvb, self.topk), cv, attn
         return self.model(starts, paths, ends, label)
 
     def _names(self, outputs):
         """(label index, probability) tensors [B, topk] on the CPU."""
-        vals, idx, lse = Fn.row_topk(outputs.detach().contiguous(), self.topk)
+        if self.fused_head:
+            vals, idx, lse = outputs
+        else:
+            vals, idx, lse = Fn.row_topk(outputs.detach().contiguous(),
+                                         self.topk)
         return idx.cpu(), Fn.topk_probs(vals, lse).cpu()
 
     @torch.no_grad()
@@ -148,8 +165,13 @@ class Predictor:
         paths = batch["paths"].to(self.device)
         ends = batch["ends"].to(self.device)
         lens = batch["lengths"]
-        outputs, code_vector, attn = self.model.forward_packed(
-            starts, paths, ends, lens)
+        if self.fused_head:
+            code_vector, cvb, attn = self.model.encode_packed(
+                starts, paths, ends, lens)
+            outputs = self.model.head_topk(cvb, self.topk)
+        else:
+            outputs, code_vector, attn = self.model.forward_packed(
+                starts, paths, ends, lens)
 
         idx_c, probs_c = self._names(outputs)
         # per-method top contexts in K19's order: the ragged attention

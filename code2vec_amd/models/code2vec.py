@@ -70,9 +70,34 @@ def init_logical_params(option, generator: Optional[torch.Generator] = None) -> 
 
 
 ANGULAR_PREDICT_ERROR = (
-    "Predictor does not support the angular-margin head: its "
+    "Predictor does not support the angular-margin head on this path: its "
     "forward needs the true label, which prediction does not "
-    "have")
+    "have; use fused_head=True / --fused_head, which scores the "
+    "margin-free logits")
+
+
+def _unit_rows(x, out=None):
+    """bf16 unit rows of x [R, EP] bf16 as the angular head's training
+    forward forms them (inv_rownorm + rowscale; EP = 128 on the device),
+    else through torch ops.  ``out``: a contiguous tensor like x to write
+    into (its address is kept)."""
+    if out is None:
+        out = torch.empty_like(x, memory_format=torch.contiguous_format)
+    if x.is_cuda and x.shape[1] == 128:
+        x = x.contiguous()
+        inv = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+        Fn.ext().inv_rownorm(x, inv)
+        Fn.ext().rowscale(x, inv, out)
+    else:
+        out.copy_(F.normalize(x.float()))
+    return out
+
+
+def _pad32(x):
+    """x [R, E] zero-padded to the next multiple of 32 columns (the oracle's
+    head_topk shares the kernel's EP contract; zeros add nothing to a dot
+    product)."""
+    return F.pad(x.detach().float(), (0, round_up(x.shape[1]) - x.shape[1]))
 
 
 def _reject_packed(model) -> None:
@@ -131,14 +156,31 @@ class Code2VecTorch(nn.Module):
         return outputs, cv, attn
 
     @torch.no_grad()
-    def forward_packed(self, starts, paths, ends, lengths):
-        """Code2VecHIP.forward_packed's contract on the oracle backend:
-        pads to the longest method of the batch, calls ``forward`` and
-        slices the attention back to ragged.  Returns (outputs [B, L],
-        code_vector [B, E], attention [M]).  (A method whose rows are all
-        PAD gets the padded row's uniform weights here, 1/n from K21; its
-        code vector is the same.)"""
-        _reject_packed(self)
+    def encode(self, starts, paths, ends):
+        """Code2VecHIP.encode's contract on the oracle backend: (code_vector
+        [B, E], the same again — fp32 stands in for the bf16 copy —,
+        attention [B, C])."""
+        assert not self.training, "encode is inference only: eval() first"
+        ccv = R.gather_concat(
+            starts, paths, ends, self.terminal_embedding, self.path_embedding
+        )
+        ccv = R.combiner(ccv, self.input_weight, self.ln_gamma, self.ln_beta)
+        attn = R.attention(ccv, self.attention_a, (starts > 0).float())
+        cv = R.code_vector(ccv, attn)
+        return cv, cv, attn
+
+    @torch.no_grad()
+    def encode_packed(self, starts, paths, ends, lengths):
+        """Code2VecHIP.encode_packed's contract on the oracle backend (pads
+        to the longest method, as ``forward_packed`` does)."""
+        assert not self.training, "encode_packed is inference only: eval() first"
+        padded, real = self._pad_packed(starts, paths, ends, lengths)
+        cv, cvb, attn = self.encode(*padded)
+        return cv, cvb, attn[real]
+
+    def _pad_packed(self, starts, paths, ends, lengths):
+        """The [B, longest] rectangles of a packed batch and the mask of
+        their real positions."""
         M = starts.numel()
         lens = R.check_packed_lengths(lengths, M)
         B, C = lens.numel(), int(lens.max())
@@ -149,7 +191,33 @@ class Code2VecTorch(nn.Module):
             buf = torch.zeros(B, C, dtype=t.dtype, device=t.device)
             buf[real] = t.reshape(-1)
             padded.append(buf)
-        label = torch.zeros(B, dtype=torch.int64, device=starts.device)
+        return padded, real
+
+    @torch.no_grad()
+    def head_topk(self, cvb, k: int):
+        """Code2VecHIP.head_topk's contract in fp32 through the oracle: the
+        default head's logits, or inverse_temp * cosine (no margin) for the
+        angular head."""
+        opt = self.option
+        if not opt.angular_margin_loss:
+            return R.head_topk(_pad32(cvb), _pad32(self.output_weight), k,
+                               bias=self.output_bias.detach(), scale=1.0)
+        return R.head_topk(_pad32(F.normalize(cvb)),
+                           _pad32(F.normalize(self.output_weight.detach())),
+                           k, bias=None, scale=opt.inverse_temp)
+
+    @torch.no_grad()
+    def forward_packed(self, starts, paths, ends, lengths):
+        """Code2VecHIP.forward_packed's contract on the oracle backend:
+        pads to the longest method of the batch, calls ``forward`` and
+        slices the attention back to ragged.  Returns (outputs [B, L],
+        code_vector [B, E], attention [M]).  (A method whose rows are all
+        PAD gets the padded row's uniform weights here, 1/n from K21; its
+        code vector is the same.)"""
+        _reject_packed(self)
+        padded, real = self._pad_packed(starts, paths, ends, lengths)
+        label = torch.zeros(real.shape[0], dtype=torch.int64,
+                            device=starts.device)
         outputs, cv, attn = self.forward(*padded, label)
         return outputs, cv, attn[real]
 
@@ -158,15 +226,7 @@ class Code2VecTorch(nn.Module):
         backend, with autograd on: pads to the longest method of the batch
         and calls ``forward``.  Returns (outputs [B, L], code_vector
         [B, E], attention [M])."""
-        M = starts.numel()
-        lens = R.check_packed_lengths(lengths, M)
-        B, C = lens.numel(), int(lens.max())
-        real = (torch.arange(C)[None, :] < lens[:, None]).to(starts.device)
-        padded = []
-        for t in (starts, paths, ends):
-            buf = torch.zeros(B, C, dtype=t.dtype, device=t.device)
-            buf[real] = t.reshape(-1)
-            padded.append(buf)
+        padded, real = self._pad_packed(starts, paths, ends, lengths)
         outputs, cv, attn = self.forward(*padded, label)
         return outputs, cv, attn[real]
 
@@ -241,7 +301,13 @@ class Code2VecHIP(nn.Module):
         )
 
     def forward(self, starts, paths, ends, label):
-        opt = self.option
+        cv, cvb, attn = self._code_vector(starts, paths, ends)
+        outputs = self._head(cvb, label)
+        return outputs, cv[:, : self.E], attn
+
+    def _code_vector(self, starts, paths, ends):
+        """K1-K9: (cv [B, EP] f32, cvb [B, EP] bf16, attn [B, C]); what
+        ``forward`` and ``encode`` share."""
         B, C = starts.shape
         starts = starts.to(torch.int32)
         paths = paths.to(torch.int32)
@@ -278,8 +344,75 @@ class Code2VecHIP(nn.Module):
             cv, attn = Fn.AttentionPool.apply(ccv, self.attention_a, starts,
                                               self.E)
             cvb = cv.to(torch.bfloat16)
-        outputs = self._head(cvb, label)
-        return outputs, cv[:, : self.E], attn
+        return cv, cvb, attn
+
+    @torch.no_grad()
+    def encode(self, starts, paths, ends):
+        """Label-free inference up to the code vector, with the kernels
+        ``forward`` launches in eval mode.  Returns (code_vector [B, E] f32,
+        cvb [B, EP] bf16 — what the head reads —, attention [B, C])."""
+        assert not self.training, "encode is inference only: eval() first"
+        cv, cvb, attn = self._code_vector(starts, paths, ends)
+        return cv[:, : self.E], cvb, attn
+
+    @torch.no_grad()
+    def encode_packed(self, starts, paths, ends, lengths):
+        """``encode`` on a packed batch (``forward_packed``'s inputs and
+        kernels).  Returns (code_vector [B, E], cvb [B, EP] bf16, attention
+        [M])."""
+        assert not self.training, "encode_packed is inference only: eval() first"
+        cv, cvb, attn = self._code_vector_packed(starts, paths, ends, lengths)
+        return cv[:, : self.E], cvb, attn
+
+    def train(self, mode: bool = True):
+        # the optimizer's kernels write parameters without touching their
+        # version counters: entering or leaving training marks the unit-row
+        # image stale (eval() on a model in eval mode changes nothing)
+        if mode != self.training:
+            self._uw_key = None
+        return super().train(mode)
+
+    def _unit_output_weight(self):
+        """Unit-row bf16 image of output_weight for the angular head.  ONE
+        buffer for the model's lifetime, refreshed IN PLACE when the
+        parameter has changed (an in-place torch op or load_state_dict bumps
+        ``_version``; a rebind moves ``data_ptr``; ``train()`` marks it
+        stale, see there): a captured graph that read it keeps a valid
+        address, and sees the new rows once this has run again."""
+        w = self.output_weight
+        key = (w._version, w.data_ptr())
+        buf = getattr(self, "_uw_buf", None)
+        if buf is None or buf.shape != w.shape or buf.device != w.device:
+            buf = torch.empty_like(w.detach(),
+                                   memory_format=torch.contiguous_format)
+            self._uw_buf, self._uw_key = buf, None
+        if getattr(self, "_uw_key", None) != key:
+            _unit_rows(w.detach(), out=buf)
+            self._uw_key = key
+        return buf
+
+    @torch.no_grad()
+    def prepare_head_topk(self) -> None:
+        """Bring what ``head_topk`` reads besides the parameters up to date
+        (the angular head's unit-row image).  ``head_topk`` does this
+        itself; a replayed graph of it cannot, so its owner calls this
+        before every replay."""
+        if self.option.angular_margin_loss:
+            self._unit_output_weight()
+
+    @torch.no_grad()
+    def head_topk(self, cvb, k: int):
+        """The k most likely labels of code vectors cvb [B, EP] bf16 and the
+        log-sum-exp over all labels, through K23: no [B, L] tensor.  Default
+        head: logits cvb . W + b.  Angular head: inverse_temp * cosine, the
+        margin-free logits its training forward gives every label but the
+        true one.  Returns (vals [B, k] f32, idx [B, k] i64, lse [B] f32)."""
+        opt = self.option
+        if not opt.angular_margin_loss:
+            return Fn.head_topk(cvb, self.output_weight, k,
+                                bias=self.output_bias.detach(), scale=1.0)
+        return Fn.head_topk(_unit_rows(cvb), self._unit_output_weight(), k,
+                            bias=None, scale=opt.inverse_temp)
 
     def _head(self, cvb, label):
         """The output head over cvb [B, EP] bf16 (padded and packed
@@ -363,6 +496,15 @@ class Code2VecHIP(nn.Module):
         is segment-local, so a method's code vector and attention do not
         depend on the rest of the batch.  Forward only."""
         _reject_packed(self)
+        cv, cvb, attn = self._code_vector_packed(starts, paths, ends, lengths)
+        outputs = Fn.OutputHead.apply(cvb, self.output_weight,
+                                      self.output_bias)
+        return outputs, cv[:, : self.E], attn
+
+    def _code_vector_packed(self, starts, paths, ends, lengths):
+        """K1-K6 + K21 on a packed batch: (cv [B, EP] f32, cvb [B, EP]
+        bf16, attn [M]); what ``forward_packed`` and ``encode_packed``
+        share."""
         M = starts.numel()
         lens = R.check_packed_lengths(lengths, M)
         starts = starts.reshape(-1).to(torch.int32).contiguous()
@@ -374,11 +516,8 @@ class Code2VecHIP(nn.Module):
         y = Fn.CombinerLNTanh.apply(
             x, self.input_weight, self.ln_gamma, self.ln_beta, self.E,
             0.0, False)
-        cv, cvb, attn = Fn.attention_pool_packed(
+        return Fn.attention_pool_packed(
             y, self.attention_a, starts, lens, self.E)
-        outputs = Fn.OutputHead.apply(cvb, self.output_weight,
-                                      self.output_bias)
-        return outputs, cv[:, : self.E], attn
 
     def loss(self, outputs, label, class_weight):
         fused = getattr(outputs, "_c2v_fused_head", None)

@@ -137,6 +137,9 @@ int sim_topk_query_tile();
 int sim_topk_row_tile();
 void launch_sim_topk(const void*, const void*, const long*, long, long, int,
                      int, int, void*, float*, long*, hipStream_t);
+void launch_head_topk(const void*, const void*, const float*, float, long,
+                      long, int, int, int, void*, float*, float*, float*,
+                      long*, float*, hipStream_t);
 void launch_head_bwd_prep(const long*, const float*, const float*,
                           const float*, const float*, float*, long,
                           hipStream_t);
@@ -1297,6 +1300,73 @@ void sim_topk(torch::Tensor q, torch::Tensor db, torch::Tensor exclude,
                   idx.data_ptr<long>(), cur_stream());
 }
 
+// K23: fused head + top-k + log-sum-exp.  q [nq, EP] bf16, w [L, EP] bf16,
+// bias f32 [L] (or an empty tensor for none); logits scale * q.w + bias are
+// never written.  vals f32 [nq, k], idx i64 [nq, k] in K19's order, lse f32
+// [nq] over all L labels.  part (i64 [nq, nsplit, 16]) and pm/ps (f32
+// [nq, nsplit]) are only touched when nsplit > 1.  query_tile/row_tile are
+// the caller's idea of the kernel's tiles (K20's).
+void head_topk(torch::Tensor q, torch::Tensor w, torch::Tensor bias,
+               double scale, int64_t k, int64_t nsplit, int64_t query_tile,
+               int64_t row_tile, torch::Tensor part, torch::Tensor pm,
+               torch::Tensor ps, torch::Tensor vals, torch::Tensor idx,
+               torch::Tensor lse) {
+  CHK_CUDA(q); CHK_CONTIG(q); CHK_DT(q, torch::kBFloat16);
+  CHK_CUDA(w); CHK_CONTIG(w); CHK_DT(w, torch::kBFloat16);
+  TORCH_CHECK(q.dim() == 2 && w.dim() == 2,
+              "head_topk: q must be [nq, EP] and w [L, EP]");
+  const long nq = q.size(0), EP = q.size(1), L = w.size(0);
+  TORCH_CHECK(w.size(1) == EP, "head_topk: q has EP = ", EP, ", w has ",
+              w.size(1));
+  TORCH_CHECK(EP % 32 == 0 && EP >= 32 && EP <= 512,
+              "head_topk: EP must be a multiple of 32 in 32..512, got ", EP);
+  TORCH_CHECK(query_tile == sim_topk_query_tile() &&
+              row_tile == sim_topk_row_tile(),
+              "head_topk: tiles ", query_tile, "x", row_tile,
+              " != compiled ", sim_topk_query_tile(), "x",
+              sim_topk_row_tile());
+  TORCH_CHECK(k >= 1 && k <= 16, "head_topk: k must be in 1..16, got ", k);
+  TORCH_CHECK(L < (1L << 31) && nq < (1L << 31),
+              "head_topk: L and nq must be < 2^31");
+  TORCH_CHECK(k <= L, "head_topk: k = ", k, " exceeds the head's ", L,
+              " labels");
+  const float sc = (float)scale;
+  TORCH_CHECK(std::isfinite(sc) && sc > 0.f,
+              "head_topk: scale must be finite and > 0, got ", scale);
+  const float* bp = nullptr;
+  if (bias.numel() > 0) {
+    CHK_CUDA(bias); CHK_CONTIG(bias); CHK_DT(bias, torch::kFloat32);
+    TORCH_CHECK(bias.dim() == 1 && bias.size(0) == L,
+                "head_topk: bias must be [L]");
+    bp = bias.data_ptr<float>();
+  }
+  const long nqt = (nq + query_tile - 1) / query_tile;
+  TORCH_CHECK(nsplit >= 1 && nsplit * std::max(nqt, 1L) < (1L << 31),
+              "head_topk: nsplit = ", nsplit, " gives an invalid grid");
+  CHK_CUDA(vals); CHK_CONTIG(vals); CHK_DT(vals, torch::kFloat32);
+  CHK_CUDA(idx); CHK_CONTIG(idx); CHK_DT(idx, torch::kInt64);
+  CHK_CUDA(lse); CHK_CONTIG(lse); CHK_DT(lse, torch::kFloat32);
+  TORCH_CHECK(vals.numel() == nq * k && idx.numel() == nq * k &&
+              lse.numel() == nq, "head_topk: output shapes");
+  void* pp = nullptr;
+  float* pmp = nullptr;
+  float* psp = nullptr;
+  if (nsplit > 1) {
+    CHK_CUDA(part); CHK_CONTIG(part); CHK_DT(part, torch::kInt64);
+    CHK_CUDA(pm); CHK_CONTIG(pm); CHK_DT(pm, torch::kFloat32);
+    CHK_CUDA(ps); CHK_CONTIG(ps); CHK_DT(ps, torch::kFloat32);
+    TORCH_CHECK(part.numel() >= nq * nsplit * 16 &&
+                pm.numel() >= nq * nsplit && ps.numel() >= nq * nsplit,
+                "head_topk: partials too small");
+    pp = part.data_ptr();
+    pmp = pm.data_ptr<float>();
+    psp = ps.data_ptr<float>();
+  }
+  launch_head_topk(q.data_ptr(), w.data_ptr(), bp, sc, nq, L, (int)EP, (int)k,
+                   (int)nsplit, pp, pmp, psp, vals.data_ptr<float>(),
+                   idx.data_ptr<long>(), lse.data_ptr<float>(), cur_stream());
+}
+
 void transpose_w(torch::Tensor w, torch::Tensor wt) {
   CHK_CUDA(w); CHK_CONTIG(w); CHK_DT(w, torch::kBFloat16);
   CHK_CONTIG(wt); CHK_DT(wt, torch::kBFloat16);
@@ -1805,6 +1875,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("row_max_argmax", &row_max_argmax);
   m.def("row_topk", &row_topk);
   m.def("sim_topk", &sim_topk);
+  m.def("head_topk", &head_topk);
   m.def("inv_rownorm", &inv_rownorm);
   m.def("rowscale", &rowscale);
   m.def("angular_fwd", &angular_fwd);

@@ -40,31 +40,10 @@
 // No atomics anywhere; bitwise reproducible; no host sync.
 
 #include "common.h"
-#include "topk_keys.h"  // key order, wave lists, rank merge (shared with K20)
+#include "topk_keys.h"  // key order, wave lists, rank merge, lse merge
 
 #define TOPK_CHUNK 32768
 #define TOPK_UNR 4
-
-// (max, sumexp) merge; an all -inf side contributes 0, never NaN
-__device__ __forceinline__ void lse_merge(float& m, float& s, float om,
-                                          float os) {
-  const float M = fmaxf(m, om);
-  if (M == NEG_INF) {
-    s = 0.f;
-    return;
-  }
-  s = s * __expf(m - M) + os * __expf(om - M);
-  m = M;
-}
-
-__device__ __forceinline__ void wave_lse_merge(float& m, float& s) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const float om = __shfl_xor(m, off);
-    const float os = __shfl_xor(s, off);
-    lse_merge(m, s, om, os);
-  }
-}
 
 template <typename T, int V>
 __device__ __forceinline__ void load_vec(const T* p, float (&out)[V]) {
@@ -275,6 +254,17 @@ void launch_row_topk(const void* x, int is_f32, long B, long L, int k,
   if (nchunk > 1)
     row_topk_stage2_kernel<<<(unsigned)B, 256, 0, stream>>>(
         pp, pm, ps, nchunk, k, vals, idx, lse);
+}
+
+// Stage 2 on its own, for K23 (head_topk.hip): its stage 1 leaves the same
+// part[B, n, 16] keys and pm/ps[B, n] pairs, one per label slice.
+void launch_row_topk_stage2(const void* part, const float* pm,
+                            const float* ps, long B, int n, int k,
+                            float* vals, long* idx, float* lse,
+                            hipStream_t stream) {
+  if (B == 0) return;
+  row_topk_stage2_kernel<<<(unsigned)B, 256, 0, stream>>>(
+      (const u64*)part, pm, ps, n, k, vals, idx, lse);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // Shared pieces of the top-k selection kernels (K19 row_topk in topk.hip,
-// K20 sim_topk in sim_topk.hip): the 64-bit total-order key, the
-// wave-cooperative sorted list and the rank merge of four wave lists.
+// K20 sim_topk in sim_topk.hip, K23 head_topk in head_topk.hip): the 64-bit
+// total-order key, the wave-cooperative sorted list, the rank merge of four
+// wave lists and the (max, sumexp) merge of the log-sum-exp.
 //
 // Total order: descending value, ties to the SMALLEST column.  Every
 // element is mapped to a unique 64-bit key
@@ -81,4 +82,25 @@ __device__ __forceinline__ int block_rank(const u64* sk, u64& my) {
     rank += (o > my || (o == my && j < lane)) ? 1 : 0;
   }
   return rank;
+}
+
+// (max, sumexp) merge; an all -inf side contributes 0, never NaN
+__device__ __forceinline__ void lse_merge(float& m, float& s, float om,
+                                          float os) {
+  const float M = fmaxf(m, om);
+  if (M == NEG_INF) {
+    s = 0.f;
+    return;
+  }
+  s = s * __expf(m - M) + os * __expf(om - M);
+  m = M;
+}
+
+__device__ __forceinline__ void wave_lse_merge(float& m, float& s) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const float om = __shfl_xor(m, off);
+    const float os = __shfl_xor(s, off);
+    lse_merge(m, s, om, os);
+  }
 }

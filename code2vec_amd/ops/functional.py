@@ -1806,6 +1806,139 @@ def sim_topk_composed(q: torch.Tensor, db: torch.Tensor, k: int,
     return vals, idx
 
 
+# K23 runs on K20's tiles (SIM_QUERY_TILE x SIM_ROW_TILE).  Label tiles a
+# slice holds by default: fixed, so the default nsplit depends on the head's
+# shape alone and a query's lse bits do not depend on the batch it is in
+# (PERF.md, "K23 fused head + top-k": the slice-width sweep; 128 sits
+# between the 32-64 small batches want and the 256-512 of nq = 1024).
+_HEAD_TOPK_SLICE_TILES = 128
+# C2V_HEAD_TOPK_FUSED=0 routes head_topk to head_topk_composed (A/B baseline)
+_HEAD_TOPK_FUSED = os.environ.get("C2V_HEAD_TOPK_FUSED", "1") == "1"
+
+
+def head_topk_default_nsplit(L: int, EP: int) -> int:
+    """Label slices K23 uses when the caller does not force a number: a
+    function of the head's shape only, never of the number of queries.
+    (The measured width is EP = 128's; other widths use it as it is.)"""
+    return max(1, -(-L // SIM_ROW_TILE) // _HEAD_TOPK_SLICE_TILES)
+
+
+def head_topk_slice_rows(L: int, nsplit: int) -> int:
+    """Labels per slice for a given nsplit (slice s owns labels
+    [s * rows, (s + 1) * rows)); exposed so tests can plant values on
+    slice boundaries."""
+    return sim_topk_slice_rows(L, nsplit)
+
+
+def _head_topk_check_device(q, w, bias):
+    if q.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
+        raise ValueError(
+            f"head_topk: device inputs must be bf16, got {q.dtype} and "
+            f"{w.dtype}")
+    if q.device != w.device or (bias is not None
+                                and bias.device != q.device):
+        raise ValueError(
+            "head_topk: q, w and bias must be on the same device")
+    if not (q.is_contiguous() and w.is_contiguous()
+            and (bias is None or bias.is_contiguous())):
+        raise ValueError("head_topk: device inputs must be contiguous")
+
+
+def head_topk(q: torch.Tensor, w: torch.Tensor, k: int, bias=None,
+              scale: float = 1.0, nsplit: Optional[int] = None):
+    """K23: per query row of q [nq, EP], the k (1..16) labels with the
+    largest logit scale * q . w[l] + bias[l] over w [L, EP] and the
+    log-sum-exp over all L logits, without materializing the [nq, L]
+    matrix.  Returns (vals f32 [nq, k], idx i64 [nq, k], lse f32 [nq]) in
+    row_topk's total order.  Device bf16 input runs the HIP kernel (no host
+    sync; capturable); CPU tensors take ops/reference.py::head_topk.
+    ``nsplit`` forces the number of label slices: vals and idx do not
+    depend on it, lse does in its last bits, which is why the default is a
+    function of (L, EP) alone."""
+    from . import reference as R
+
+    k = int(k)
+    scale = float(scale)
+    R.check_head_topk_args(q, w, k, bias, scale)
+    if not (q.is_cuda or w.is_cuda):
+        return R.head_topk(q, w, k, bias, scale)
+    _head_topk_check_device(q, w, bias)
+    if not _HEAD_TOPK_FUSED:
+        return head_topk_composed(q, w, k, bias, scale)
+    if not hasattr(ext(), "head_topk"):
+        # a missing kernel is an error, never a quiet change of path
+        raise RuntimeError(
+            "head_topk: the built extension has no K23 kernel; rebuild it "
+            "(python setup.py build_ext --inplace)")
+    nq, EP = q.shape
+    L = w.shape[0]
+    dev = q.device
+    if nsplit is None:
+        nsplit = head_topk_default_nsplit(L, EP)
+    nsplit = int(nsplit)
+    if nsplit < 1:
+        raise ValueError(f"head_topk: nsplit must be >= 1, got {nsplit}")
+    vals = torch.empty(nq, k, dtype=torch.float32, device=dev)
+    idx = torch.empty(nq, k, dtype=torch.int64, device=dev)
+    lse = torch.empty(nq, dtype=torch.float32, device=dev)
+    if nq == 0:
+        return vals, idx, lse
+    if nsplit > 1:
+        part = torch.empty(nq, nsplit, 16, dtype=torch.int64, device=dev)
+        pm = torch.empty(nq, nsplit, dtype=torch.float32, device=dev)
+        ps = torch.empty_like(pm)
+    else:
+        part = pm = ps = _NONE_T
+    ext().head_topk(q, w, bias if bias is not None else _NONE_T, scale, k,
+                    nsplit, SIM_QUERY_TILE, SIM_ROW_TILE, part, pm, ps, vals,
+                    idx, lse)
+    return vals, idx, lse
+
+
+def head_topk_composed(q: torch.Tensor, w: torch.Tensor, k: int, bias=None,
+                       scale: float = 1.0, bf16_logits: bool = False):
+    """head_topk's contract through existing parts, in query chunks sized so
+    the logits stay under about 1 GiB: an fp32 matmul, then row_topk (K19).
+    The A/B baseline of the fused kernel; logits differ from K23's only by
+    fp32 summation order.  ``bf16_logits=True`` is the prediction path as it
+    was before K23, for timing it: OutputHead's bf16 [chunk, L] logits, then
+    K19 (default head only: a bias and scale == 1)."""
+    from . import reference as R
+
+    k = int(k)
+    scale = float(scale)
+    R.check_head_topk_args(q, w, k, bias, scale)
+    if q.is_cuda or w.is_cuda:
+        _head_topk_check_device(q, w, bias)
+    if bf16_logits and (bias is None or scale != 1.0):
+        raise ValueError(
+            "head_topk_composed: bf16_logits is the default head's path "
+            "(a bias and scale == 1)")
+    nq, L = q.shape[0], w.shape[0]
+    dev = q.device
+    vals = torch.empty(nq, k, dtype=torch.float32, device=dev)
+    idx = torch.empty(nq, k, dtype=torch.int64, device=dev)
+    lse = torch.empty(nq, dtype=torch.float32, device=dev)
+    wt = None if bf16_logits else w.float().t()
+    step = max(1, _SIM_COMPOSED_SCORE_BYTES // ((2 if bf16_logits else 4) * L))
+    for a in range(0, nq, step):
+        b = min(nq, a + step)
+        if bf16_logits:
+            with torch.no_grad():
+                z = OutputHead.apply(q[a:b], w, bias)
+        else:
+            z = q[a:b].float() @ wt
+            if scale != 1.0:
+                z *= scale
+            if bias is not None:
+                z += bias
+        v, i, s = row_topk(z, k)
+        vals[a:b] = v
+        idx[a:b] = i
+        lse[a:b] = s
+    return vals, idx, lse
+
+
 def adam_step(
     param: torch.Tensor,
     grad: torch.Tensor,

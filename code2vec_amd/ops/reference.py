@@ -168,6 +168,51 @@ def sim_topk(q, db, k: int, exclude=None):
     return row_topk(S, k)[:2]
 
 
+def check_head_topk_args(q, w, k: int, bias=None, scale: float = 1.0) -> None:
+    """Argument contract shared by the oracle and the HIP op (K23)."""
+    if q.dim() != 2 or w.dim() != 2:
+        raise ValueError(
+            f"head_topk: q must be [nq, EP] and w [L, EP], got "
+            f"{tuple(q.shape)} and {tuple(w.shape)}")
+    EP, L = q.shape[1], w.shape[0]
+    if w.shape[1] != EP:
+        raise ValueError(
+            f"head_topk: q has EP = {EP}, w has EP = {w.shape[1]}")
+    if EP % 32 != 0 or not 32 <= EP <= SIM_TOPK_MAX_EP:
+        raise ValueError(
+            f"head_topk: EP must be a multiple of 32 in "
+            f"32..{SIM_TOPK_MAX_EP}, got {EP}")
+    if not 1 <= k <= ROW_TOPK_MAX_K:
+        raise ValueError(
+            f"head_topk: k must be in 1..{ROW_TOPK_MAX_K}, got {k}")
+    if L >= 1 << 31:
+        raise ValueError("head_topk: L must be < 2^31")
+    if k > L:
+        raise ValueError(f"head_topk: k = {k} exceeds the head's {L} labels")
+    if bias is not None and (bias.dim() != 1 or bias.shape[0] != L
+                             or bias.dtype != torch.float32):
+        raise ValueError(f"head_topk: bias must be float32 [{L}]")
+    scale = float(scale)
+    if not (math.isfinite(scale) and scale > 0.0):
+        # a non-positive scale would reverse or flatten the order
+        raise ValueError(
+            f"head_topk: scale must be finite and > 0, got {scale}")
+
+
+def head_topk(q, w, k: int, bias=None, scale: float = 1.0):
+    """K23: the k most likely labels of a head without its logits matrix.
+    Logits z[i, l] = scale * sum_e q[i, e] w[l, e] + bias[l] in fp32;
+    selection in row_topk's total order (descending value, ties to the
+    smallest label); lse over all L labels.  A ``bias`` entry of -inf masks
+    a label: it adds nothing to lse and sorts below every finite logit.
+    Returns (vals f32 [nq, k], idx i64 [nq, k], lse f32 [nq])."""
+    check_head_topk_args(q, w, k, bias, scale)
+    z = float(scale) * (q.float() @ w.float().t())
+    if bias is not None:
+        z = z + bias.to(z.device)
+    return row_topk(z, k)
+
+
 def logsoftmax_nll(logits, label, weight):
     """K12: log_softmax + weighted NLL (reference main.py:251-264 with the
     criterion built at main.py:129-130).

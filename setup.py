@@ -26,6 +26,7 @@ SRC = [
     "code2vec_amd/ops/csrc/colsum.hip",
     "code2vec_amd/ops/csrc/topk.hip",
     "code2vec_amd/ops/csrc/sim_topk.hip",
+    "code2vec_amd/ops/csrc/head_topk.hip",
     "code2vec_amd/ops/csrc/head_fwd.hip",
     "code2vec_amd/ops/csrc/head_dgrad.hip",
     "code2vec_amd/ops/csrc/head_bwd.hip",
@@ -54,7 +55,10 @@ setup(
             sources=SRC,
             extra_compile_args={
                 "cxx": ["-O3", "-std=c++17"],
-                "nvcc": ["-O3", "-std=c++17", "--offload-arch=gfx950"],
+                # the remarks print registers, LDS, scratch and spills of
+                # every kernel (PERF.md's resource tables)
+                "nvcc": ["-O3", "-std=c++17", "--offload-arch=gfx950",
+                         "-Rpass-analysis=kernel-resource-usage"],
             },
         )
     ],

@@ -19,6 +19,11 @@ By default a method goes through the training layout: padded to
 --random_seed).  --all_contexts predicts from every context of every
 method instead (packed batches, no padding, no subsampling, no seed).
 
+--fused_head takes the names straight from the code vectors (K23): the
+[methods, labels] logits matrix is never allocated, and a model trained
+with --angular_margin_loss can predict (give both flags, and the run's
+--inverse_temp); it is scored by its margin-free logits.
+
     python tools/predict.py --model output/code2vec.model \\
         --corpus_path dataset/corpus.txt \\
         --path_idx_path dataset/path_idxs.txt \\
@@ -85,6 +90,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--max_path_length", type=int, default=200)
     p.add_argument("--angular_margin_loss", action="store_true",
                    default=False)
+    p.add_argument("--inverse_temp", type=float, default=30.0,
+                   help="the angular-margin head's logit scale (main.py's)")
+    p.add_argument("--fused_head", action="store_true", default=False,
+                   help="names through the fused head + top-k kernel: no "
+                        "[methods, labels] logits; required for an "
+                        "--angular_margin_loss model")
     return p
 
 
@@ -97,14 +108,21 @@ def _mismatch(what: str, have: int, tensor: str, want: int) -> SystemExit:
 def check_checkpoint(sd, reader, args) -> None:
     """One-line error naming both numbers for every size that disagrees
     with the checkpoint tensors."""
-    if "output_linear" in sd and "output_linear.weight" not in sd:
+    angular = "output_linear" in sd and "output_linear.weight" not in sd
+    if angular and not (args.angular_margin_loss and args.fused_head):
         raise SystemExit(
             "predict: the checkpoint has an angular-margin head, which "
-            "cannot be scored without labels")
+            "the default path cannot score without labels; add "
+            "--angular_margin_loss --fused_head")
+    if args.angular_margin_loss and not angular:
+        raise SystemExit(
+            "predict: --angular_margin_loss given, but the checkpoint has "
+            "a default head (output_linear.weight)")
     term = sd["terminal_embedding.weight"]
     path = sd["path_embedding.weight"]
     w_in = sd["input_linear.weight"]
-    w_out = sd["output_linear.weight"]
+    out_name = "output_linear" if angular else "output_linear.weight"
+    w_out = sd[out_name]
     checks = [
         ("terminal_embed_size", args.terminal_embed_size,
          "terminal_embedding.weight.shape[1]", term.shape[1]),
@@ -117,7 +135,7 @@ def check_checkpoint(sd, reader, args) -> None:
         ("path count", len(reader.path_vocab),
          "path_embedding.weight.shape[0]", path.shape[0]),
         ("label count", len(reader.label_vocab),
-         "output_linear.weight.shape[0]", w_out.shape[0]),
+         f"{out_name}.shape[0]", w_out.shape[0]),
     ]
     for what, have, tensor, want in checks:
         if int(have) != int(want):
@@ -167,6 +185,7 @@ def main(argv=None) -> int:
         dropout_prob=0.0,
         batch_size=args.batch_size,
         angular_margin_loss=args.angular_margin_loss,
+        inverse_temp=args.inverse_temp,
         device=device,
     )
     backend = args.backend
@@ -181,7 +200,8 @@ def main(argv=None) -> int:
                               batch_size=args.batch_size,
                               seed=args.random_seed,
                               all_contexts=args.all_contexts,
-                              max_batch_contexts=args.max_batch_contexts)
+                              max_batch_contexts=args.max_batch_contexts,
+                              fused_head=args.fused_head)
     except ValueError as e:
         raise SystemExit(f"predict: {e}") from e
 
