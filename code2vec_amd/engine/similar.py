@@ -22,6 +22,7 @@ from ..ops import reference as R
 
 METRICS = ("cosine", "dot")
 MAX_K = R.ROW_TOPK_MAX_K
+DEFAULT_MAX_PAIRS = R.SIM_RANGE_MAX_PAIRS
 _EPS = 1e-12  # keeps a zero vector zero under cosine normalization
 _FORMAT = "code2vec_amd.CodeVectorIndex.v1"
 
@@ -211,3 +212,109 @@ class CodeVectorIndex:
                 f"rows must be in [0, {len(self)})")
         q = self.matrix.index_select(0, rows).contiguous()
         return self._search_prepared(q, k, rows)
+
+    # -- range search (K24) --------------------------------------------------
+    def _check_rows(self, rows) -> torch.Tensor:
+        rows = torch.as_tensor(rows, dtype=torch.int64).to(self.device)
+        if rows.dim() != 1:
+            raise ValueError("rows must be a 1-D list of index rows")
+        if rows.numel() and (int(rows.min()) < 0
+                             or int(rows.max()) >= len(self)):
+            raise ValueError(f"rows must be in [0, {len(self)})")
+        return rows.contiguous()
+
+    def range_search(self, queries: torch.Tensor, threshold: float,
+                     exclude_rows=None, max_pairs: int = DEFAULT_MAX_PAIRS):
+        """queries [nq, E] float -> CSR (offsets i64 [nq + 1], rows i64
+        [nnz], scores f32 [nnz]): query i owns
+        rows[offsets[i]:offsets[i + 1]], EVERY index row with a score of at
+        least ``threshold``, in ascending row order.  exclude_rows [nq]: one
+        index row per query that must not come back (-1: none).  More than
+        ``max_pairs`` results raise a ValueError."""
+        q = self._prepare(queries, "queries")
+        if exclude_rows is not None:
+            exclude_rows = torch.as_tensor(exclude_rows).to(
+                self.device, torch.int64).contiguous()
+            if exclude_rows.dim() != 1 \
+                    or exclude_rows.shape[0] != q.shape[0]:
+                raise ValueError("exclude_rows must hold one row per query")
+        return Fn.sim_range(q, self.matrix, threshold, exclude=exclude_rows,
+                            max_pairs=max_pairs)
+
+    def neighbors_within(self, rows, threshold: float,
+                         max_pairs: int = DEFAULT_MAX_PAIRS):
+        """Index rows as queries, each excluding itself: the range-search
+        counterpart of neighbors_of_rows.  Returns range_search's CSR."""
+        rows = self._check_rows(rows)
+        q = self.matrix.index_select(0, rows).contiguous()
+        return Fn.sim_range(q, self.matrix, threshold, exclude=rows,
+                            max_pairs=max_pairs)
+
+    def duplicate_pairs(self, threshold: float, query_chunk: int = 16384,
+                        max_pairs: int = DEFAULT_MAX_PAIRS):
+        """The self-join: every unordered pair of index rows with a score of
+        at least ``threshold``, once.  Returns CPU tensors (i i64, j i64,
+        score f32) with i < j, sorted by (i, j).  The index is its own
+        query set, ``query_chunk`` rows per range search, each row looking
+        only at the rows after it; the result does not depend on
+        ``query_chunk``.  ``max_pairs`` bounds the total."""
+        query_chunk = int(query_chunk)
+        if query_chunk < 1:
+            raise ValueError(
+                f"query_chunk must be >= 1, got {query_chunk}")
+        R.check_sim_range_args(self.matrix[:0], self.matrix, threshold,
+                               max_pairs=max_pairs)
+        N = len(self)
+        out_i, out_j, out_s = [], [], []
+        total = 0
+        for a in range(0, N, query_chunk):
+            b = min(N, a + query_chunk)
+            own = torch.arange(a, b, dtype=torch.int64, device=self.device)
+            try:
+                offsets, rows, scores = Fn.sim_range(
+                    self.matrix[a:b], self.matrix, threshold, after=own,
+                    max_pairs=max_pairs - total)
+            except R.TooManyPairs as e:
+                raise R.TooManyPairs(total + e.total, e.threshold,
+                                     max_pairs) from None
+            total += rows.shape[0]
+            out_i.append(torch.repeat_interleave(
+                own, offsets.diff()).cpu())
+            out_j.append(rows.cpu())
+            out_s.append(scores.cpu())
+        return torch.cat(out_i), torch.cat(out_j), torch.cat(out_s)
+
+    def duplicate_groups(self, threshold: float, query_chunk: int = 16384,
+                         max_pairs: int = DEFAULT_MAX_PAIRS):
+        """Groups of near-duplicates: the connected components of the graph
+        whose edges are duplicate_pairs(threshold).  This is single
+        linkage: similarity above a threshold is not transitive, so a group
+        may hold two members that score BELOW the threshold to each other
+        (A ~ B and B ~ C put A and C together).  Returns a list of row
+        lists, each ascending, ordered by their smallest member (the
+        group's representative); rows without a partner are omitted."""
+        i, j, _ = self.duplicate_pairs(threshold, query_chunk, max_pairs)
+        return _components(i, j, len(self))
+
+
+def _components(i: torch.Tensor, j: torch.Tensor, n: int) -> List[List[int]]:
+    """Connected components of the edges (i, j) over n nodes by min-label
+    propagation to a fixed point: every node ends with the smallest node of
+    its component.  Components of one node are left out."""
+    if i.numel() == 0:
+        return []
+    label = torch.arange(n, dtype=torch.int64)
+    while True:
+        m = torch.minimum(label[i], label[j])
+        new = label.scatter_reduce(0, i, m, "amin")
+        new = new.scatter_reduce(0, j, m, "amin")
+        new = new[new]  # pointer jumping: a label's own label is no larger
+        if torch.equal(new, label):
+            break
+        label = new
+    members = torch.unique(torch.cat((i, j)))  # ascending
+    lab = label[members]
+    order = torch.sort(lab, stable=True).indices
+    members, lab = members[order], lab[order]
+    sizes = torch.unique_consecutive(lab, return_counts=True)[1].tolist()
+    return [g.tolist() for g in torch.split(members, sizes)]

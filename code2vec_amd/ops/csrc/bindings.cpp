@@ -137,6 +137,13 @@ int sim_topk_query_tile();
 int sim_topk_row_tile();
 void launch_sim_topk(const void*, const void*, const long*, long, long, int,
                      int, int, void*, float*, long*, hipStream_t);
+int sim_range_waves();
+void launch_sim_range_count(const void*, const void*, const long*,
+                            const long*, float, long, long, int, int, int*,
+                            hipStream_t);
+void launch_sim_range_fill(const void*, const void*, const long*, const long*,
+                           float, long, long, int, int, const long*, long,
+                           long*, float*, hipStream_t);
 void launch_head_topk(const void*, const void*, const float*, float, long,
                       long, int, int, int, void*, float*, float*, float*,
                       long*, float*, hipStream_t);
@@ -1300,6 +1307,99 @@ void sim_topk(torch::Tensor q, torch::Tensor db, torch::Tensor exclude,
                   idx.data_ptr<long>(), cur_stream());
 }
 
+// K24: similarity range search, checks shared by its two passes.  Returns
+// the number of (query, slice, wave) segments, nq * nsplit * waves.
+static long sim_range_check(const char* op, const torch::Tensor& q,
+                            const torch::Tensor& db,
+                            const torch::Tensor& exclude,
+                            const torch::Tensor& after, double threshold,
+                            int64_t nsplit, int64_t query_tile,
+                            int64_t row_tile, int64_t waves,
+                            const long** ex, const long** af) {
+  CHK_CUDA(q); CHK_CONTIG(q); CHK_DT(q, torch::kBFloat16);
+  CHK_CUDA(db); CHK_CONTIG(db); CHK_DT(db, torch::kBFloat16);
+  TORCH_CHECK(q.dim() == 2 && db.dim() == 2, op,
+              ": q must be [nq, EP] and db [N, EP]");
+  const long nq = q.size(0), EP = q.size(1), N = db.size(0);
+  TORCH_CHECK(db.size(1) == EP, op, ": q has EP = ", EP, ", db has ",
+              db.size(1));
+  TORCH_CHECK(EP % 32 == 0 && EP >= 32 && EP <= 512, op,
+              ": EP must be a multiple of 32 in 32..512, got ", EP);
+  TORCH_CHECK(query_tile == sim_topk_query_tile() &&
+              row_tile == sim_topk_row_tile() && waves == sim_range_waves(),
+              op, ": tiles ", query_tile, "x", row_tile, " in ", waves,
+              " waves != compiled ", sim_topk_query_tile(), "x",
+              sim_topk_row_tile(), " in ", sim_range_waves());
+  TORCH_CHECK(N >= 1 && N < (1L << 31) && nq < (1L << 31), op,
+              ": N must be in 1..2^31-1 and nq < 2^31");
+  TORCH_CHECK(std::isfinite((float)threshold), op,
+              ": threshold must be finite in fp32, got ", threshold);
+  *ex = nullptr;
+  if (exclude.numel() > 0) {
+    CHK_CUDA(exclude); CHK_CONTIG(exclude); CHK_DT(exclude, torch::kInt64);
+    TORCH_CHECK(exclude.dim() == 1 && exclude.size(0) == nq, op,
+                ": exclude must be [nq]");
+    *ex = exclude.data_ptr<long>();
+  }
+  *af = nullptr;
+  if (after.numel() > 0) {
+    CHK_CUDA(after); CHK_CONTIG(after); CHK_DT(after, torch::kInt64);
+    TORCH_CHECK(after.dim() == 1 && after.size(0) == nq, op,
+                ": after must be [nq]");
+    *af = after.data_ptr<long>();
+  }
+  const long nqt = (nq + query_tile - 1) / query_tile;
+  TORCH_CHECK(nsplit >= 1 && nsplit * std::max(nqt, 1L) < (1L << 31), op,
+              ": nsplit = ", nsplit, " gives an invalid grid");
+  return nq * nsplit * waves;
+}
+
+// K24 count pass: counts i32 [nq, nsplit, waves] = hits of every (query,
+// slice, wave), in the order the fill pass writes them.
+void sim_range_count(torch::Tensor q, torch::Tensor db, torch::Tensor exclude,
+                     torch::Tensor after, double threshold, int64_t nsplit,
+                     int64_t query_tile, int64_t row_tile, int64_t waves,
+                     torch::Tensor counts) {
+  const long *ex, *af;
+  const long nseg = sim_range_check("sim_range_count", q, db, exclude, after,
+                                    threshold, nsplit, query_tile, row_tile,
+                                    waves, &ex, &af);
+  CHK_CUDA(counts); CHK_CONTIG(counts); CHK_DT(counts, torch::kInt32);
+  TORCH_CHECK(counts.numel() == nseg, "sim_range_count: counts must hold ",
+              nseg, " entries");
+  launch_sim_range_count(q.data_ptr(), db.data_ptr(), ex, af,
+                         (float)threshold, q.size(0), db.size(0),
+                         (int)q.size(1), (int)nsplit,
+                         counts.data_ptr<int>(), cur_stream());
+}
+
+// K24 fill pass: cur i64 [nq * nsplit * waves + 1] are the exclusive
+// cursors of the count pass run with the same arguments (last entry: the
+// total); rows i64 [nnz] and scores f32 [nnz] receive the hits.
+void sim_range_fill(torch::Tensor q, torch::Tensor db, torch::Tensor exclude,
+                    torch::Tensor after, double threshold, int64_t nsplit,
+                    int64_t query_tile, int64_t row_tile, int64_t waves,
+                    torch::Tensor cur, torch::Tensor rows,
+                    torch::Tensor scores) {
+  const long *ex, *af;
+  const long nseg = sim_range_check("sim_range_fill", q, db, exclude, after,
+                                    threshold, nsplit, query_tile, row_tile,
+                                    waves, &ex, &af);
+  CHK_CUDA(cur); CHK_CONTIG(cur); CHK_DT(cur, torch::kInt64);
+  CHK_CUDA(rows); CHK_CONTIG(rows); CHK_DT(rows, torch::kInt64);
+  CHK_CUDA(scores); CHK_CONTIG(scores); CHK_DT(scores, torch::kFloat32);
+  TORCH_CHECK(cur.numel() == nseg + 1, "sim_range_fill: cur must hold ",
+              nseg + 1, " entries");
+  TORCH_CHECK(rows.dim() == 1 && scores.dim() == 1 &&
+              rows.numel() == scores.numel(),
+              "sim_range_fill: rows and scores must be [nnz]");
+  launch_sim_range_fill(q.data_ptr(), db.data_ptr(), ex, af,
+                        (float)threshold, q.size(0), db.size(0),
+                        (int)q.size(1), (int)nsplit, cur.data_ptr<long>(),
+                        rows.numel(), rows.data_ptr<long>(),
+                        scores.data_ptr<float>(), cur_stream());
+}
+
 // K23: fused head + top-k + log-sum-exp.  q [nq, EP] bf16, w [L, EP] bf16,
 // bias f32 [L] (or an empty tensor for none); logits scale * q.w + bias are
 // never written.  vals f32 [nq, k], idx i64 [nq, k] in K19's order, lse f32
@@ -1875,6 +1975,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("row_max_argmax", &row_max_argmax);
   m.def("row_topk", &row_topk);
   m.def("sim_topk", &sim_topk);
+  m.def("sim_range_count", &sim_range_count);
+  m.def("sim_range_fill", &sim_range_fill);
   m.def("head_topk", &head_topk);
   m.def("inv_rownorm", &inv_rownorm);
   m.def("rowscale", &rowscale);

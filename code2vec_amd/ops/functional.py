@@ -1806,6 +1806,183 @@ def sim_topk_composed(q: torch.Tensor, db: torch.Tensor, k: int,
     return vals, idx
 
 
+# K24 runs on K20's tiles; the waves of a block split their slice into
+# contiguous runs (the extension checks the number against the compiled one).
+SIM_RANGE_WAVES = 4
+# blocks the default nsplit aims for per pass: one per CU of a 256-CU
+# device.  K24 has no lists to merge, so longer runs per wave cost nothing
+# (PERF.md, "K24 similarity range search": the nsplit sweep)
+_SIM_RANGE_TARGET_BLOCKS = 256
+# tiles a slice should at least hold (16 per wave): below that the query
+# fragments and the pipeline prologue are loaded for a handful of MFMAs
+_SIM_RANGE_MIN_SLICE_TILES = 64
+SIM_RANGE_MAX_PAIRS = 1 << 24
+
+
+def sim_range_default_nsplit(nq: int, N: int) -> int:
+    """Index slices K24 uses when the caller does not force a number."""
+    nqt = max(1, -(-nq // SIM_QUERY_TILE))
+    ntile = -(-N // SIM_ROW_TILE)
+    return max(1, min(-(-_SIM_RANGE_TARGET_BLOCKS // nqt),
+                      ntile // _SIM_RANGE_MIN_SLICE_TILES))
+
+
+def sim_range_slice_rows(N: int, nsplit: int) -> int:
+    """Index rows per slice for a given nsplit (slice s owns rows
+    [s * rows, (s + 1) * rows)); exposed so tests can plant rows on slice
+    boundaries."""
+    return sim_topk_slice_rows(N, nsplit)
+
+
+def sim_range_wave_rows(N: int, nsplit: int) -> int:
+    """Index rows per wave within a slice: wave w of slice s owns rows
+    [s * slice_rows + w * wave_rows, ... + wave_rows), cut at the slice's
+    end; exposed so tests can plant rows on wave boundaries."""
+    tiles = sim_topk_slice_rows(N, nsplit) // SIM_ROW_TILE
+    return -(-tiles // SIM_RANGE_WAVES) * SIM_ROW_TILE
+
+
+def _sim_range_check_device(q, db, exclude, after):
+    if q.dtype != torch.bfloat16 or db.dtype != torch.bfloat16:
+        raise ValueError(
+            f"sim_range: device inputs must be bf16, got {q.dtype} and "
+            f"{db.dtype}")
+    if q.device != db.device:
+        raise ValueError("sim_range: q and db must be on the same device")
+    if not (q.is_contiguous() and db.is_contiguous()):
+        raise ValueError("sim_range: device inputs must be contiguous")
+    for name, t in (("exclude", exclude), ("after", after)):
+        if t is not None and (t.device != q.device
+                              or not t.is_contiguous()):
+            raise ValueError(
+                f"sim_range: {name} must be contiguous on the inputs' "
+                f"device")
+
+
+def sim_range_count(q, db, threshold, exclude=None, after=None,
+                    nsplit: Optional[int] = None):
+    """K24's count pass on checked device inputs: (cur i64 [nq * nsplit *
+    4 + 1], nsplit) — the exclusive write cursors of every (query, slice,
+    wave), the total last.  No host sync."""
+    nq, N = q.shape[0], db.shape[0]
+    if nsplit is None:
+        nsplit = sim_range_default_nsplit(nq, N)
+    nsplit = int(nsplit)
+    if nsplit < 1:
+        raise ValueError(f"sim_range: nsplit must be >= 1, got {nsplit}")
+    counts = torch.empty(nq, nsplit, SIM_RANGE_WAVES, dtype=torch.int32,
+                         device=q.device)
+    ext().sim_range_count(q, db, exclude if exclude is not None else _NONE_T,
+                          after if after is not None else _NONE_T,
+                          threshold, nsplit, SIM_QUERY_TILE, SIM_ROW_TILE,
+                          SIM_RANGE_WAVES, counts)
+    cur = torch.zeros(counts.numel() + 1, dtype=torch.int64, device=q.device)
+    cur[1:] = torch.cumsum(counts.view(-1), 0, dtype=torch.int64)
+    return cur, nsplit
+
+
+def sim_range_fill(q, db, threshold, cur, nsplit: int, total: int,
+                   exclude=None, after=None):
+    """K24's fill pass: (offsets, rows, scores) from sim_range_count's
+    cursors and their total (cur[-1], read back by the caller)."""
+    nq = q.shape[0]
+    dev = q.device
+    offsets = cur[::nsplit * SIM_RANGE_WAVES].contiguous()
+    rows = torch.empty(total, dtype=torch.int64, device=dev)
+    scores = torch.empty(total, dtype=torch.float32, device=dev)
+    if total:
+        ext().sim_range_fill(
+            q, db, exclude if exclude is not None else _NONE_T,
+            after if after is not None else _NONE_T, threshold, nsplit,
+            SIM_QUERY_TILE, SIM_ROW_TILE, SIM_RANGE_WAVES, cur, rows, scores)
+    assert offsets.shape[0] == nq + 1
+    return offsets, rows, scores
+
+
+def sim_range(q: torch.Tensor, db: torch.Tensor, threshold: float,
+              exclude=None, after=None,
+              max_pairs: int = SIM_RANGE_MAX_PAIRS,
+              nsplit: Optional[int] = None):
+    """K24: per query row of q [nq, EP], EVERY row of db [N, EP] whose dot
+    product is at least fp32(threshold), without materializing the [nq, N]
+    score matrix.  Returns a CSR (offsets i64 [nq + 1], rows i64 [nnz],
+    scores f32 [nnz]): query i owns rows[offsets[i]:offsets[i + 1]],
+    strictly ascending; a score has the bits sim_topk gives the same pair.
+    ``exclude`` [nq] i64: one index row per query that is never reported
+    (-1: none).  ``after`` [nq] i64: only rows > after[i] are reported
+    (-1: all), which makes a self-join emit every unordered pair once.
+    More than ``max_pairs`` pairs raise a ValueError
+    (reference.TooManyPairs) before any output is allocated.
+
+    Device bf16 input runs the HIP kernel in two passes (count, fill) with
+    ONE host sync between them — the total is read back to size the
+    outputs, as for torch.nonzero — so the op is NOT graph-capturable.  CPU
+    tensors take ops/reference.py::sim_range.  ``nsplit`` forces the number
+    of index slices (results do not depend on it)."""
+    from . import reference as R
+
+    R.check_sim_range_args(q, db, threshold, exclude, after, max_pairs)
+    if not (q.is_cuda or db.is_cuda):
+        return R.sim_range(q, db, threshold, exclude, after, max_pairs)
+    _sim_range_check_device(q, db, exclude, after)
+    t32 = R.sim_range_threshold(threshold)
+    nq = q.shape[0]
+    dev = q.device
+    if nsplit is not None and int(nsplit) < 1:
+        raise ValueError(f"sim_range: nsplit must be >= 1, got {nsplit}")
+    if nq == 0:
+        return (torch.zeros(1, dtype=torch.int64, device=dev),
+                torch.empty(0, dtype=torch.int64, device=dev),
+                torch.empty(0, dtype=torch.float32, device=dev))
+    cur, nsplit = sim_range_count(q, db, t32, exclude, after, nsplit)
+    total = int(cur[-1])  # the op's one host sync
+    if total > max_pairs:
+        raise R.TooManyPairs(total, t32, max_pairs)
+    return sim_range_fill(q, db, t32, cur, nsplit, total, exclude, after)
+
+
+def sim_range_composed(q: torch.Tensor, db: torch.Tensor, threshold: float,
+                       exclude=None, after=None,
+                       max_pairs: int = SIM_RANGE_MAX_PAIRS):
+    """sim_range's contract through existing parts: an fp32 matmul per
+    query chunk (chunks sized so the scores stay under about 1 GiB), then
+    >= and nonzero.  The A/B baseline of the fused kernel and a test
+    reference; scores differ from K24's only by fp32 summation order.  One
+    host sync per chunk."""
+    from . import reference as R
+
+    R.check_sim_range_args(q, db, threshold, exclude, after, max_pairs)
+    if q.is_cuda or db.is_cuda:
+        _sim_range_check_device(q, db, exclude, after)
+    t32 = R.sim_range_threshold(threshold)
+    nq, N = q.shape[0], db.shape[0]
+    dev = q.device
+    dbt = db.float().t()
+    step = max(1, _SIM_COMPOSED_SCORE_BYTES // (4 * N))
+    counts = torch.zeros(nq, dtype=torch.int64, device=dev)
+    rows, scores = [], []
+    total = 0
+    for a in range(0, nq, step):
+        b = min(nq, a + step)
+        S = q[a:b].float() @ dbt
+        mask = R.sim_range_mask(
+            S, t32, None if exclude is None else exclude[a:b],
+            None if after is None else after[a:b])
+        counts[a:b] = mask.sum(dim=1)
+        total += int(counts[a:b].sum())
+        if total > max_pairs:
+            raise R.TooManyPairs(total, t32, max_pairs)
+        hit = torch.nonzero(mask)
+        rows.append(hit[:, 1])
+        scores.append(S[hit[:, 0], hit[:, 1]])
+    offsets = torch.zeros(nq + 1, dtype=torch.int64, device=dev)
+    offsets[1:] = torch.cumsum(counts, 0)
+    if not rows:
+        return (offsets, torch.empty(0, dtype=torch.int64, device=dev),
+                torch.empty(0, dtype=torch.float32, device=dev))
+    return offsets, torch.cat(rows), torch.cat(scores)
+
+
 # K23 runs on K20's tiles (SIM_QUERY_TILE x SIM_ROW_TILE).  Label tiles a
 # slice holds by default: fixed, so the default nsplit depends on the head's
 # shape alone and a query's lse bits do not depend on the batch it is in

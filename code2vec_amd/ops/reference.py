@@ -168,6 +168,103 @@ def sim_topk(q, db, k: int, exclude=None):
     return row_topk(S, k)[:2]
 
 
+SIM_RANGE_MAX_PAIRS = 1 << 24
+
+
+class TooManyPairs(ValueError):
+    """sim_range counted more pairs than ``max_pairs`` allows."""
+
+    def __init__(self, total: int, threshold: float, max_pairs: int):
+        super().__init__(
+            f"sim_range: {total} pairs score at least the threshold "
+            f"{threshold}, more than max_pairs = {max_pairs}; raise the "
+            f"threshold or max_pairs")
+        self.total = total
+        self.threshold = threshold
+        self.max_pairs = max_pairs
+
+
+def sim_range_threshold(threshold) -> float:
+    """The threshold as the fp32 value every comparison uses."""
+    try:
+        t = float(threshold)
+    except (TypeError, ValueError):
+        raise ValueError(
+            f"sim_range: threshold must be a number, got {threshold!r}")
+    t32 = float(torch.tensor(t, dtype=torch.float32)) if math.isfinite(t) \
+        else t
+    if not math.isfinite(t32):
+        raise ValueError(
+            f"sim_range: threshold must be finite in fp32, got {threshold}")
+    return t32
+
+
+def check_sim_range_args(q, db, threshold, exclude=None, after=None,
+                         max_pairs: int = SIM_RANGE_MAX_PAIRS) -> None:
+    """Argument contract shared by the oracle and the HIP op (K24)."""
+    if q.dim() != 2 or db.dim() != 2:
+        raise ValueError(
+            f"sim_range: q must be [nq, EP] and db [N, EP], got "
+            f"{tuple(q.shape)} and {tuple(db.shape)}")
+    EP, N = q.shape[1], db.shape[0]
+    if db.shape[1] != EP:
+        raise ValueError(
+            f"sim_range: q has EP = {EP}, db has EP = {db.shape[1]}")
+    if EP % 32 != 0 or not 32 <= EP <= SIM_TOPK_MAX_EP:
+        raise ValueError(
+            f"sim_range: EP must be a multiple of 32 in "
+            f"32..{SIM_TOPK_MAX_EP}, got {EP}")
+    if not 1 <= N < 1 << 31:
+        raise ValueError(f"sim_range: N must be in 1..2^31-1, got {N}")
+    sim_range_threshold(threshold)
+    for name, t in (("exclude", exclude), ("after", after)):
+        if t is not None and (not torch.is_tensor(t) or t.dim() != 1
+                              or t.shape[0] != q.shape[0]
+                              or t.dtype != torch.int64):
+            raise ValueError(f"sim_range: {name} must be int64 [nq]")
+    if isinstance(max_pairs, bool) or not isinstance(max_pairs, int) \
+            or max_pairs < 0:
+        raise ValueError(
+            f"sim_range: max_pairs must be an integer >= 0, got {max_pairs!r}")
+
+
+def sim_range_mask(S, t32: float, exclude=None, after=None):
+    """Allowed pairs of a score block S [n, N] f32 (exclude/after [n])."""
+    mask = S >= torch.tensor(t32, dtype=torch.float32, device=S.device)
+    if exclude is not None or after is not None:
+        cols = torch.arange(S.shape[1], device=S.device).view(1, -1)
+        if exclude is not None:
+            mask &= cols != exclude.to(S.device).view(-1, 1)
+        if after is not None:
+            mask &= cols > after.to(S.device).view(-1, 1)
+    return mask
+
+
+def sim_range(q, db, threshold, exclude=None, after=None,
+              max_pairs: int = SIM_RANGE_MAX_PAIRS):
+    """K24: every index row of ``db`` whose dot product with a query row of
+    ``q`` is at least fp32(threshold), as a CSR: (offsets i64 [nq + 1],
+    rows i64 [nnz], scores f32 [nnz]); query i owns
+    rows[offsets[i]:offsets[i + 1]], strictly ascending.  ``exclude`` [nq]
+    i64 names one row per query that is never reported (-1: none);
+    ``after`` [nq] i64 admits only rows > after[i] (-1: all).  More than
+    ``max_pairs`` pairs raise TooManyPairs (a ValueError)."""
+    check_sim_range_args(q, db, threshold, exclude, after, max_pairs)
+    t32 = sim_range_threshold(threshold)
+    nq = q.shape[0]
+    S = q.float() @ db.float().t()
+    mask = sim_range_mask(S, t32, exclude, after)
+    counts = mask.sum(dim=1)
+    total = int(counts.sum())
+    if total > max_pairs:
+        raise TooManyPairs(total, t32, max_pairs)
+    offsets = torch.zeros(nq + 1, dtype=torch.int64, device=S.device)
+    offsets[1:] = torch.cumsum(counts, 0)
+    # nonzero is row-major: ascending query, then ascending index row
+    hit = torch.nonzero(mask)
+    return offsets, hit[:, 1].contiguous(), S[hit[:, 0], hit[:, 1]]
+
+
 def check_head_topk_args(q, w, k: int, bias=None, scale: float = 1.0) -> None:
     """Argument contract shared by the oracle and the HIP op (K23)."""
     if q.dim() != 2 or w.dim() != 2:

@@ -26,6 +26,7 @@ SRC = [
     "code2vec_amd/ops/csrc/colsum.hip",
     "code2vec_amd/ops/csrc/topk.hip",
     "code2vec_amd/ops/csrc/sim_topk.hip",
+    "code2vec_amd/ops/csrc/sim_range.hip",
     "code2vec_amd/ops/csrc/head_topk.hip",
     "code2vec_amd/ops/csrc/head_fwd.hip",
     "code2vec_amd/ops/csrc/head_dgrad.hip",

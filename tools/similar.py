@@ -14,7 +14,17 @@ One JSON object per query, in input order:
 
     {"query": i, "name": ..., "neighbors": [{"row", "name", "score"}]}
 
+--k K lists the K best rows (at most 16); --threshold T lists EVERY row
+that scores at least T instead, best first, however many there are.  With
+--self --threshold T, --groups writes the groups of near-duplicates (the
+connected components of the pairs scoring at least T), one per line:
+
+    {"group": g, "size": n, "representative": {"row", "name"},
+     "members": [{"row", "name"}, ...]}
+
     python tools/similar.py --vectors output/code.vec --self --k 5
+    python tools/similar.py --vectors output/code.vec --self \\
+        --threshold 0.95 --groups
     python tools/predict.py ... --with_vector --out preds.jsonl
     python tools/similar.py --vectors output/code.vec \\
         --query_predictions preds.jsonl
@@ -24,12 +34,14 @@ from __future__ import annotations
 
 import argparse
 import json
+import math
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 MAX_K = 16
+DEFAULT_K = 5
 # queries per search call: bounds the host-side result handling, the
 # kernel itself takes any number
 QUERY_CHUNK = 4096
@@ -51,8 +63,19 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--self", dest="self_search", action="store_true",
                    default=False,
                    help="every index row against all the others")
-    p.add_argument("--k", type=int, default=5,
-                   help=f"neighbours per query (1..{MAX_K})")
+    p.add_argument("--k", type=int, default=None,
+                   help=f"neighbours per query (1..{MAX_K}; default "
+                        f"{DEFAULT_K} unless --threshold is given)")
+    p.add_argument("--threshold", type=float, default=None,
+                   help="list every row scoring at least this instead of "
+                        "the --k best")
+    p.add_argument("--groups", action="store_true", default=False,
+                   help="with --self --threshold: write groups of "
+                        "near-duplicates instead of per-query lists")
+    p.add_argument("--max_pairs", type=int, default=None,
+                   help="with --threshold: give up beyond this many "
+                        "results per search call, or pairs in all with "
+                        "--groups (default 2^24)")
     p.add_argument("--metric", type=str, default=None,
                    choices=["cosine", "dot"],
                    help="default: cosine for --vectors, the saved one for "
@@ -101,7 +124,23 @@ def _read_predictions(path):
 def main(argv=None) -> int:
     parser = build_parser()
     args = parser.parse_args(argv)
-    if not 1 <= args.k <= MAX_K:
+    if args.threshold is not None and args.k is not None:
+        raise SystemExit(
+            "similar: --k and --threshold are mutually exclusive")
+    if args.groups and not (args.self_search and args.threshold is not None):
+        raise SystemExit("similar: --groups needs --self and --threshold")
+    if args.max_pairs is not None and args.threshold is None:
+        raise SystemExit("similar: --max_pairs needs --threshold")
+    if args.max_pairs is not None and args.max_pairs < 0:
+        raise SystemExit(
+            f"similar: --max_pairs must be >= 0, got {args.max_pairs}")
+    if args.threshold is not None and not math.isfinite(args.threshold):
+        raise SystemExit(
+            f"similar: --threshold must be finite, got {args.threshold}")
+    ranged = args.threshold is not None
+    if not ranged and args.k is None:
+        args.k = DEFAULT_K
+    if not ranged and not 1 <= args.k <= MAX_K:
         raise SystemExit(f"similar: --k must be in 1..{MAX_K}, got {args.k}")
     if (args.vectors is None) == (args.index is None):
         raise SystemExit(
@@ -141,15 +180,16 @@ def main(argv=None) -> int:
         index.save(args.save_index)
 
     N = len(index)
+    range_kw = {} if args.max_pairs is None else {"max_pairs": args.max_pairs}
     if args.self_search:
-        if args.k >= N:
+        if not ranged and args.k >= N:
             raise SystemExit(
                 f"similar: --self needs --k below the index's {N} rows, "
                 f"got {args.k}")
         q_names, q_vecs = index.names, None
         nq = N
     else:
-        if args.k > N:
+        if not ranged and args.k > N:
             raise SystemExit(
                 f"similar: --k {args.k} exceeds the index's {N} rows")
         try:
@@ -171,8 +211,54 @@ def main(argv=None) -> int:
 
     out = open(args.out, "w", encoding="utf-8") if args.out else sys.stdout
     try:
+        if args.groups:
+            try:
+                groups = index.duplicate_groups(args.threshold, **range_kw)
+            except ValueError as e:
+                raise SystemExit(f"similar: {e}") from e
+            for g, members in enumerate(groups):
+                out.write(json.dumps({
+                    "group": g,
+                    "size": len(members),
+                    "representative": {"row": members[0],
+                                       "name": index.names[members[0]]},
+                    "members": [{"row": r, "name": index.names[r]}
+                                for r in members],
+                }) + "\n")
+            extra = sum(len(m) - 1 for m in groups)
+            print(f"similar: {N} methods, {len(groups)} groups, {extra} "
+                  f"rows that are not a representative", file=sys.stderr)
+            return 0
         for a in range(0, nq, QUERY_CHUNK):
             b = min(nq, a + QUERY_CHUNK)
+            if ranged:
+                try:
+                    if q_vecs is None:
+                        csr = index.neighbors_within(
+                            torch.arange(a, b), args.threshold, **range_kw)
+                    else:
+                        csr = index.range_search(
+                            q_vecs[a:b], args.threshold, **range_kw)
+                except ValueError as e:
+                    raise SystemExit(f"similar: {e}") from e
+                offsets, rows, scores = (t.cpu() for t in csr)
+                offsets = offsets.tolist()
+                for i in range(b - a):
+                    r = rows[offsets[i]:offsets[i + 1]]
+                    s = scores[offsets[i]:offsets[i + 1]]
+                    # best first; rows come ascending, so a stable sort
+                    # leaves equal scores by ascending row
+                    order = torch.sort(s, descending=True,
+                                       stable=True).indices
+                    out.write(json.dumps({
+                        "query": a + i,
+                        "name": q_names[a + i],
+                        "neighbors": [
+                            {"row": rr, "name": index.names[rr], "score": ss}
+                            for rr, ss in zip(r[order].tolist(),
+                                              s[order].tolist())],
+                    }) + "\n")
+                continue
             try:
                 if q_vecs is None:
                     scores, rows = index.neighbors_of_rows(
